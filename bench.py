@@ -16,6 +16,15 @@ tokens/s = N*S*K / max-over-ranks elapsed. Inputs: torch.randn seed
 csrc/benchmarks/flash_bench.cu:40-41).
 
 Rank 0 prints ONE JSON line (driver contract).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the line. --dump-outputs DIR additionally saves
+the schedule-independent rows of the last timed step's output as
+DIR/moe_out.npy (float32, [n, H]) with their token indices in
+DIR/moe_out_rows.npy (see schedule_independent_rows). Everything
+else the benchmark measures (per-phase roofline of the expert GEMM pair,
+the CPU-oracle baseline, the N>1 overlap-efficiency probe) runs only
+with --full; without it those keys are null.
 """
 import argparse
 import ctypes
@@ -106,6 +115,37 @@ def measure_roofline(moe, lib, x, gw, ew, S, H, P, E, EC, iters=10):
     }
 
 
+def schedule_independent_rows(lib, S, E, EC, top_k):
+    """Token rows of the last forward's output whose value does not depend
+    on block scheduling, for --dump-outputs.
+
+    In this workload (capacity_factor 1) some experts receive more than EC
+    tokens. WHICH of them such an expert keeps follows the inter-tile
+    arrival order (as in the reference), so the output rows of every token
+    that selected an overflowing expert can change from run to run. The
+    raw per-expert counts, and hence the set of overflowing experts, are
+    fixed by the seeded inputs; a token that holds all top_k of its slots
+    in experts that did not fill up is computed the same way every run.
+    An expert whose clipped count equals EC is treated as overflowing."""
+    import numpy as np
+
+    import flashmoe_amd._ext as _ext
+
+    counts = np.zeros(E, dtype=np.uint32)
+    tok = np.zeros(E * EC, dtype=np.uint32)
+    ps = np.zeros(E * EC, dtype=np.float32)
+    _ext.check(lib.fm_read_routing(
+        None, ctypes.c_void_p(counts.ctypes.data),
+        ctypes.c_void_p(tok.ctypes.data), ctypes.c_void_p(ps.ctypes.data)),
+        "fm_read_routing")
+    tok = tok.reshape(E, EC)
+    slots = np.zeros(S, dtype=np.int64)
+    for e in range(E):
+        if counts[e] < EC:
+            np.add.at(slots, tok[e, :counts[e]] & 0x0FFFFFFF, 1)
+    return np.nonzero(slots == top_k)[0]
+
+
 def measure_cpu_baseline(cfg, target_seconds=15.0):
     """Oracle (kind 'port') on this box's host cores: a bounded sample of
     the same workload, scaled to tokens/s."""
@@ -146,8 +186,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline phases, the CPU-oracle "
+                         "baseline and (N>1) the overlap-efficiency probe")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the schedule-independent rows of the last "
+                         "timed step's output to DIR/moe_out.npy (float32) "
+                         "and their token indices to DIR/moe_out_rows.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch
 
@@ -195,8 +245,9 @@ def main():
         step()
     barrier()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     barrier()
     elapsed = time.perf_counter() - t0
     if distributed:
@@ -212,7 +263,7 @@ def main():
     # overlap efficiency (N>1 only): t(compute-only, comms stubbed)/t(full)
     # per the reference's overlap-efficiency concept (README.md:33-35)
     overlap_eff = None
-    if distributed:
+    if args.full and distributed:
         from flashmoe_amd import ep
 
         k2 = max(10, args.steps // 4)
@@ -232,9 +283,19 @@ def main():
         overlap_eff = round(t_stub / (elapsed / args.steps), 4)
 
     if rank == 0:
+        if args.dump_outputs:
+            import numpy as np
+
+            rows = schedule_independent_rows(lib, S, E, EC,
+                                             cfg["expert_top_k"])
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "moe_out.npy"),
+                    out.view(S, H).float().cpu().numpy()[rows])
+            np.save(os.path.join(args.dump_outputs, "moe_out_rows.npy"),
+                    rows.astype(np.float64))
         roofline = None
         cpu_baseline = None
-        if world == 1:
+        if args.full and world == 1:
             roofline = measure_roofline(moe, lib, x.view(S, H), gw, ew, S, H,
                                         P, E, EC)
             if not args.skip_cpu_baseline:

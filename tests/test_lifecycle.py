@@ -16,7 +16,7 @@ from tests.conftest import REPO_ROOT
 def test_bench_contract_static():
     """bench.py carries the driver contract: flags, JSON keys, workload."""
     src = open(os.path.join(REPO_ROOT, "bench.py")).read()
-    for flag in ["--gpus", "--steps", "--warmup"]:
+    for flag in ["--gpus", "--steps", "--warmup", "--full", "--dump-outputs"]:
         assert flag in src
     for key in ['"metric"', '"value"', '"unit"', '"n_gpus"', '"steps"',
                 '"warmup"', '"ms_per_step"', '"higher_is_better"',
