@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/flashmoe_abi.h"
 
@@ -112,6 +113,16 @@ template <> struct ETr<bf16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   }
   static __device__ __forceinline__ bf16 fromf(float v) { return __float2bfloat16(v); }
+  // two conversions packed into one dword: ONE v_cvt_pk_bf16_f32 with
+  // both sources (fromf compiles to the same instruction with one
+  // source, so the rounding is identical)
+  static __device__ __forceinline__ uint32_t pack2(float x, float y) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+    const bf16x2v r = __builtin_convertvector(f32x2n{x, y}, bf16x2v);
+    uint32_t w;
+    __builtin_memcpy(&w, &r, 4);
+    return w;
+  }
 };
 template <> struct ETr<fp16> {
   using vec8 = halfx8;
@@ -119,6 +130,13 @@ template <> struct ETr<fp16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
   }
   static __device__ __forceinline__ fp16 fromf(float v) { return __float2half(v); }
+  static __device__ __forceinline__ uint32_t pack2(float x, float y) {
+    typedef __attribute__((ext_vector_type(2))) _Float16 halfx2v;
+    const halfx2v r = __builtin_convertvector(f32x2n{x, y}, halfx2v);
+    uint32_t w;
+    __builtin_memcpy(&w, &r, 4);
+    return w;
+  }
 };
 
 // hidden_act 0: ReLU, 1: exact-erf GELU (cutlass epilogue::thread::{ReLU,
@@ -774,12 +792,35 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
 // Same phase semantics/epilogues as k_group_gemm_bf16.
 // ---------------------------------------------------------------------------
 
+// -DFM_GEMM_STAMPS (measurement build only, tools/gemm_phase_stamps.py):
+// thread 0 of each block records the constant 100 MHz wall clock at job
+// entry, first MFMA, end of K-loop and end of epilogue of every big-tile
+// job and writes the four stamps to g_gemmStamps[PHASE][block][job].
+// The default build contains none of this.
+#ifdef FM_GEMM_STAMPS
+constexpr int FM_STAMP_PHASES = 4, FM_STAMP_BLOCKS = 512, FM_STAMP_JOBS = 4;
+__device__ unsigned long long
+    g_gemmStamps[FM_STAMP_PHASES][FM_STAMP_BLOCKS][FM_STAMP_JOBS][4];
+#define FM_STAMP(i)                                                           \
+  do {                                                                        \
+    if (threadIdx.x == 0) fmStamp[i] = __builtin_amdgcn_s_memrealtime();      \
+  } while (0)
+#else
+#define FM_STAMP(i) do {} while (0)
+#endif
+
 // effective staging depth for a (BM, BN, WET, STAGES) tile: degrade
 // triple buffering to double when it would not fit the 160 KB LDS
+// per-row epilogue metadata behind the stage buffers: two copies (job
+// parity) of sTps[BM] (8 B) and sScale[BM] (4 B), plus a 16-B pad
+__host__ __device__ constexpr int gemm_meta_bytes(int BM) {
+  return 2 * BM * 8 + 2 * BM * 4 + 16;
+}
+
 template <int BM, int BN, int BEZ, int STAGES>
 constexpr int gemm_se() {
-  return (STAGES == 3 &&
-          3 * BM * 64 * 2 + 3 * BN * 64 * BEZ + BM * 8 + 16 > 160 * 1024)
+  return (STAGES == 3 && 3 * BM * 64 * 2 + 3 * BN * 64 * BEZ +
+                                 gemm_meta_bytes(BM) > 160 * 1024)
              ? 2 : STAGES;
 }
 
@@ -788,7 +829,34 @@ constexpr int gemm_se() {
 template <int BM, int BN, int BEZ, int STAGES>
 constexpr int gemm_lds_bytes() {
   constexpr int SE = gemm_se<BM, BN, BEZ, STAGES>();
-  return SE * BM * 64 * 2 + SE * BN * 64 * BEZ + BM * 8 + 16;
+  return SE * BM * 64 * 2 + SE * BN * 64 * BEZ + gemm_meta_bytes(BM);
+}
+
+// compile-time bool handed to the epilogue's generic lambda
+template <bool B> struct BoolC { static constexpr bool value = B; };
+
+// Four consecutive output columns of one row (col0 .. col0+3, nValid of
+// them inside N) from one lane. Wide path: packed conversion + ONE 8-byte
+// store (16-byte for fp32). SC1 keeps the agent-scope write-through of
+// storeElem on the wide word (relaxed atomic store at agent scope ->
+// global_store_dwordx2 ... sc1). A group that straddles N, or a row base
+// that is not wide-aligned (vecOK false), falls back to element stores.
+template <bool SC1, typename ET>
+__device__ __forceinline__ void storeRow4(ET* p, const float (&v)[4],
+                                          int nValid, bool vecOK) {
+  if (vecOK && nValid >= 4) {
+    const uint64_t w = (uint64_t)ETr<ET>::pack2(v[0], v[1]) |
+                       ((uint64_t)ETr<ET>::pack2(v[2], v[3]) << 32);
+    if constexpr (SC1)
+      __hip_atomic_store(reinterpret_cast<uint64_t*>(p), w, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    else
+      *reinterpret_cast<uint64_t*>(p) = w;
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < nValid) storeElem(p + r, ETr<ET>::fromf(v[r]), SC1);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -798,12 +866,26 @@ constexpr int gemm_lds_bytes() {
 // runtime here; the classic kernels pass template constants that fold
 // after inlining. Layout/state contracts documented at the kernel below.
 // ---------------------------------------------------------------------------
+// RT_SC1: honour a.sc1Out (agent-scope write-through epilogue stores).
+// Only the fused kernel has in-launch consumers, so only its walks
+// instantiate the sc1 epilogues; the classic kernels compile them out.
 template <typename ET, int PHASE, int BN, int BM, typename WET, int STAGES,
-          int CK = 0, int CN = 0>
+          int CK = 0, int CN = 0, bool RT_SC1 = false>
 __device__ __forceinline__ bool gemm_job_body(
     const GemmArgs& a, char* smemBase, int e, int ksplit, int m0, int n0,
-    int act, bool hasBias) {
+    int act, bool hasBias, int par, int jobLocal = 0) {
+  // par: which copy of the per-row metadata (sTps/sScale) this job uses.
+  // The caller flips it after every job that RAN: a job then never
+  // rewrites the copy the previous job's epilogue may still be reading
+  // (every wave passes a barrier of job t+1 before job t+2 starts), so
+  // no barrier is needed between one job's epilogue and the next
+  // job's prologue. An empty job passes no barrier and must not flip.
   using vec8 = typename ETr<ET>::vec8;
+#ifdef FM_GEMM_STAMPS
+  unsigned long long fmStamp[4] = {0, 0, 0, 0};
+#endif
+  (void)jobLocal;
+  FM_STAMP(0);
   constexpr int BK = 64;
   constexpr int NF = BN / 64;           // B fragments per wave (4 or 2)
   constexpr int MI = BM / 32;           // A fragments per wave (8 or 4)
@@ -817,8 +899,9 @@ __device__ __forceinline__ bool gemm_job_body(
   ET* Abase = reinterpret_cast<ET*>(smemBase);      // SE x [BM][BK]
   WET* Bbase = reinterpret_cast<WET*>(smemBase + SE * BM * BK * 2);
   TPS* sTps = reinterpret_cast<TPS*>(
-      smemBase + SE * BM * BK * 2 + SE * BN * BK * BEZ);
-  uint32_t* sRouted = reinterpret_cast<uint32_t*>(sTps + BM);
+      smemBase + SE * BM * BK * 2 + SE * BN * BK * BEZ) + par * BM;
+  float* sScale = reinterpret_cast<float*>(
+      smemBase + SE * BM * BK * 2 + SE * BN * BK * BEZ + 2 * BM * 8) + par * BM;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -835,21 +918,18 @@ __device__ __forceinline__ bool gemm_job_body(
   const int kStart = ksplit * kLen;
 
   const TPS* tpsE = a.tokenIds ? a.tokenIds + (size_t)e * a.pEC : nullptr;
-  __syncthreads();  // job t-1's epilogue sTps/sScale readers done
-  if (tid == 0)
-    *sRouted = tpsE ? min(a.eC[e], (uint32_t)a.EC) : (uint32_t)a.nRows;
-  __syncthreads();
-  const uint32_t routed = *sRouted;
-  if ((uint32_t)m0 >= routed) return false;  // empty tile
+  // routed count: every wave reads it itself (no LDS round trip, no
+  // barrier) and makes it wave-uniform. An agent-scope load, not a
+  // scalar-cache one: in the fused kernel eC is produced earlier in the
+  // SAME launch, which the scalar cache is not coherent with.
+  uint32_t routed = (uint32_t)a.nRows;
+  if (tpsE)
+    routed = min((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(
+                     a.eC + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)),
+                 (uint32_t)a.EC);
+  if ((uint32_t)m0 >= routed) return false;  // empty tile (block-uniform)
   const int mCap = a.tokenIds ? a.pEC : a.nRows;  // A-row clamp bound
   const int we = a.segExpert ? a.segExpert[e] : e;  // weight/bias expert
-  if (tid < BM) {
-    TPS t{0u, 1.0f};
-    if ((uint32_t)(m0 + tid) < routed)
-      t = tpsE ? tpsE[m0 + tid] : TPS{(uint32_t)(m0 + tid), 1.0f};
-    sTps[tid] = t;
-  }
-  __syncthreads();
 
   const ET* __restrict__ Ag = reinterpret_cast<const ET*>(a.A);
   const WET* __restrict__ Bg =
@@ -866,12 +946,18 @@ __device__ __forceinline__ bool gemm_job_body(
   const size_t aBase = (size_t)e * a.strideAExpert;  // 0 for the x-gather up phase
   const ET* aSrc[GPW_A];
   const WET* bSrc[GPW_B];
+  // The staging lanes load the routing entries of their own A rows
+  // straight from global (8 lanes share a row): no LDS round trip sits
+  // between tokenIds and the first A stage. Issued FIRST, so the B half
+  // of stage 0 below overlaps their latency.
+  TPS tpsv[GPW_A];
 #pragma unroll
   for (int i = 0; i < GPW_A; ++i) {
     const int row = (wave * GPW_A + i) * 8 + grow8;
-    const size_t arow = (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
-                                     : (size_t)min(m0 + row, mCap - 1);
-    aSrc[i] = Ag + aBase + arow * aRowStride + kStart + schunk * 8;
+    TPS t{0u, 1.0f};
+    if ((uint32_t)(m0 + row) < routed)
+      t = tpsE ? tpsE[m0 + row] : TPS{(uint32_t)(m0 + row), 1.0f};
+    tpsv[i] = t;
   }
 #pragma unroll
   for (int i = 0; i < GPW_B; ++i) {
@@ -879,12 +965,14 @@ __device__ __forceinline__ bool gemm_job_body(
     bSrc[i] = Bg + (size_t)min(n0 + row, N - 1) * K + kStart + bsc * (16 / BEZ);
   }
 
-  auto stage = [&](int kt, int buf) {
+  auto stageA = [&](int kt, int buf) {
 #pragma unroll
     for (int i = 0; i < GPW_A; ++i)
       __builtin_amdgcn_global_load_lds(
           (gas_u32*)(aSrc[i] + kt),
           (las_u32*)(Abase + buf * BM * BK + (wave * GPW_A + i) * 512), 16, 0, 0);
+  };
+  auto stageB = [&](int kt, int buf) {
 #pragma unroll
     for (int i = 0; i < GPW_B; ++i)
       __builtin_amdgcn_global_load_lds(
@@ -892,6 +980,44 @@ __device__ __forceinline__ bool gemm_job_body(
           (las_u32*)((char*)Bbase + buf * BN * BK * BEZ +
                      (wave * GPW_B + i) * 1024), 16, 0, 0);
   };
+  auto stage = [&](int kt, int buf) {
+    stageA(kt, buf);
+    stageB(kt, buf);
+  };
+
+  // prologue: the B half of stage 0 (weights depend on nothing) goes out
+  // before the A source rows are known
+  stageB(0, 0);
+#pragma unroll
+  for (int i = 0; i < GPW_A; ++i) {
+    const int row = (wave * GPW_A + i) * 8 + grow8;
+    const size_t arow = (PHASE == 0) ? (size_t)tpsTok(tpsv[i].tokenIdx)
+                                     : (size_t)min(m0 + row, mCap - 1);
+    aSrc[i] = Ag + aBase + arow * aRowStride + kStart + schunk * 8;
+  }
+  stageA(0, 0);
+  // slot: write the per-(token, j) combine slot; scaled only at k>1
+  // (the reference's k==1 CombineMode::single semantics are unscaled,
+  // processor.cuh:173-204)
+  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled = (PHASE == 1) && a.topk > 1;
+  // PHASE 1 row scale (gate prob / probSum): fetched here, once per row,
+  // so it is in LDS long before the epilogue and needs no barrier of its
+  // own. Issued BEFORE the second prologue stage: the counted vmcnt
+  // below then still leaves exactly that stage's GPT loads outstanding.
+  const bool metaLane = (lane & 7) == 0;  // one lane per A row
+  ET gateRaw[GPW_A];
+  if constexpr (PHASE == 1) {
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i) {
+      const int row = (wave * GPW_A + i) * 8 + grow8;
+      gateRaw[i] = ETr<ET>::fromf(0.0f);
+      if (scaled && metaLane && (uint32_t)(m0 + row) < routed)
+        gateRaw[i] = reinterpret_cast<const ET*>(
+            a.gate_out)[(size_t)tpsTok(tpsv[i].tokenIdx) * a.PX +
+                        a.expertOffset + e];
+    }
+  }
 
   const int wr = wave >> 2, wc = wave & 3;  // 2M x 4N wave grid
   f32x4 accv[MI][NF];
@@ -905,7 +1031,7 @@ __device__ __forceinline__ bool gemm_job_body(
   // vmcnt(0)+barrier per tile (the drain is cheap: the stage had the
   // whole compute phase to land).
   const int nK = kLen / BK;
-  stage(0, 0);
+  // (stage 0 was issued in the prologue above, B half first)
   if constexpr (SE == 3) {
     if (nK > 1) {
       stage(BK, 1);
@@ -916,7 +1042,22 @@ __device__ __forceinline__ bool gemm_job_body(
   } else {
     wait_vmcnt<0>();
   }
+  // per-row epilogue metadata into this job's copy; the barrier below
+  // (the first one every wave passes) publishes it
+  if (metaLane) {
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i) {
+      const int row = (wave * GPW_A + i) * 8 + grow8;
+      sTps[row] = tpsv[i];
+      if constexpr (PHASE == 1)
+        sScale[row] = toF(gateRaw[i]) / tpsv[i].probSum;
+    }
+  }
+  // raw barrier (a __syncthreads would drain the in-flight tile 1):
+  // the metadata ds_writes are the only LDS ops outstanding
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
+  FM_STAMP(1);
   for (int t = 0; t < nK; ++t) {
     // STAGES==2: staggered staging - waves 0-3 stage tile t+1 before
     // their first MFMA half, waves 4-7 between the halves, so on each
@@ -978,7 +1119,12 @@ __device__ __forceinline__ bool gemm_job_body(
         for (int mi = 2 * g2; mi < 2 * g2 + 2; ++mi)
 #pragma unroll
           for (int ni = 0; ni < NF; ++ni)
-            accv[mi][ni] = ETr<ET>::mfma(af[mi], bfr[ni], accv[mi][ni]);
+            // operands swapped (B fragment first): the accumulator then
+            // holds C^T's layout - lane & 15 is the output ROW and
+            // 4 * (lane >> 4) + r are four CONSECUTIVE output columns, so
+            // the epilogue stores a row's columns as one wide word. Same
+            // dot products in the same K order.
+            accv[mi][ni] = ETr<ET>::mfma(bfr[ni], af[mi], accv[mi][ni]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -993,92 +1139,144 @@ __device__ __forceinline__ bool gemm_job_body(
     __builtin_amdgcn_s_barrier();  // readers done AND next tile ready
   }
 
-  // epilogue (same semantics as k_group_gemm_bf16)
-  const int cl = lane & 15;
-  const int r0 = (lane >> 4) * 4;
-  float* sScale = reinterpret_cast<float*>(Abase);
-  // slot: write the per-(token, j) combine slot; scaled only at k>1
-  // (the reference's k==1 CombineMode::single semantics are unscaled,
-  // processor.cuh:173-204)
-  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
-  const bool scaled = (PHASE == 1) && a.topk > 1;
-  if constexpr (PHASE == 1) {
-    if (scaled) {
-      __syncthreads();
-      if (tid < BM) {
-        const TPS tp = sTps[tid];
-        float sc = 0.0f;
-        if ((uint32_t)(m0 + tid) < routed)
-          sc = toF(reinterpret_cast<const ET*>(
-                   a.gate_out)[(size_t)tpsTok(tp.tokenIdx) * a.PX +
-                               a.expertOffset + e]) / tp.probSum;
-        sScale[tid] = sc;
-      }
-      __syncthreads();
-    }
-  }
-  float bv[NF];
+  FM_STAMP(2);
+  // epilogue (same semantics as k_group_gemm_bf16). Swapped-operand
+  // accumulator layout: lane & 15 is the row inside fragment mi, and
+  // accv[mi][ni][0..3] are columns cq..cq+3 of fragment ni - so the row
+  // predicate, the sTps/sScale lookup and the row's output address are
+  // formed once per (lane, mi), and each (mi, ni) is one wide store.
+  // Reads only sTps/sScale of this job's copy: the stage buffers are
+  // free for the next job's prologue as soon as the K-loop ends.
+  const int rl16 = lane & 15;
+  const int cq = (lane >> 4) * 4;
+  const int nBase = n0 + wc * (BN / 4) + cq;  // column of accv[.][0][0]
+  float bv[NF][4];
 #pragma unroll
-  for (int ni = 0; ni < NF; ++ni) bv[ni] = 0.f;
+  for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[ni][r] = 0.f;
   if (hasBias && ksplit == 0) {  // split partials add the bias exactly once
     // per-expert bias slabs when multi-expert (see the 128^2 kernel)
     const ET* bptr = reinterpret_cast<const ET*>(a.bias) +
                      (a.strideBExpert ? (size_t)we * N : 0);
 #pragma unroll
-    for (int ni = 0; ni < NF; ++ni) {
-      const int col = n0 + wc * (BN / 4) + ni * 16 + cl;
-      if (col < N) bv[ni] = toF(bptr[col]);
-    }
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = nBase + ni * 16 + r;
+        if (col < N) bv[ni][r] = toF(bptr[col]);
+      }
   }
+  // per-expert / per-tile output base, hoisted out of the element loops;
+  // wide stores need every row base 8-byte (fp32: 16-byte) aligned
+  using OT = typename std::conditional<PHASE == 3, float, ET>::type;
+  OT* outBase;
+  long long rowPitch;  // elements between consecutive output rows
+  if constexpr (PHASE == 1) {
+    outBase = reinterpret_cast<OT*>(slot ? a.O32 : a.moe_out);
+    rowPitch = a.H;
+  } else if constexpr (PHASE == 3) {
+    outBase = reinterpret_cast<OT*>(a.out);
+    rowPitch = N;
+  } else {
+    outBase = reinterpret_cast<OT*>(a.out) + (size_t)e * a.strideOExpert;
+    rowPitch = N;
+  }
+  const bool vecOK =
+      (rowPitch & 3) == 0 &&
+      (reinterpret_cast<uintptr_t>(outBase) & (4 * sizeof(OT) - 1)) == 0;
+
+  // interior tile (every column group wholly inside N, rows wide-
+  // aligned): no column predicate at all. Ragged tiles take the checked
+  // instantiation.
+  const bool fullN = vecOK && (n0 + BN <= N);
+
+  // one instantiation per cache policy and per interior/ragged: the sc1
+  // (agent-scope write-through) choice and the column checks are ONE
+  // block-uniform branch per epilogue, not one per store
+  auto epilogue = [&](auto sc1c, auto fullc) {
+    constexpr bool SC1 = decltype(sc1c)::value;
+    constexpr bool FULL = decltype(fullc)::value;
 #pragma unroll
-  for (int mi = 0; mi < MI; ++mi) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = wr * (BM / 2) + mi * 16 + r0 + r;
+    for (int mi = 0; mi < MI; ++mi) {
+      const int row = wr * (BM / 2) + mi * 16 + rl16;
       const int m = m0 + row;
-      if ((uint32_t)m >= routed) continue;
-      const TPS tp = sTps[row];
-      const float rowScale = scaled ? sScale[row] : 1.0f;
+      if ((uint32_t)m >= routed) continue;  // rows past routed: not written
+      OT* orow;
+      float rowScale = 1.0f;
+      if constexpr (PHASE == 1) {
+        const TPS tp = sTps[row];
+        if (slot) {
+          // non-atomic per-(token, j) combine slot (summed with the
+          // kept mask in k_cast_combine; replaces fp32 atomics)
+          orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * a.topk +
+                            tpsJ(tp.tokenIdx)) * rowPitch;
+          if (scaled) rowScale = sScale[row];
+        } else {
+          orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+        }
+      } else {
+        orow = outBase + (size_t)m * rowPitch;
+      }
 #pragma unroll
       for (int ni = 0; ni < NF; ++ni) {
-        const int col = n0 + wc * (BN / 4) + ni * 16 + cl;
-        if (col >= N) continue;
-        float v = accv[mi][ni][r] + bv[ni];
-        if constexpr (PHASE == 0) {
-          v = (act == 0) ? fmaxf(v, 0.0f)
-                         : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
-          storeElem(&reinterpret_cast<ET*>(a.out)[(size_t)e * a.strideOExpert +
-                                                  (size_t)m * N + col],
-                    ETr<ET>::fromf(v), a.sc1Out != 0);
-        } else if constexpr (PHASE == 1) {
-          if (slot) {
-            // non-atomic per-(token, j) combine slot (summed with the
-            // kept mask in k_cast_combine; replaces fp32 atomics)
-            storeElem(&reinterpret_cast<ET*>(a.O32)[
-                          ((size_t)tpsTok(tp.tokenIdx) * a.topk +
-                           tpsJ(tp.tokenIdx)) * a.H + col],
-                      ETr<ET>::fromf(v * rowScale), a.sc1Out != 0);
-          } else {
-            reinterpret_cast<ET*>(
-                a.moe_out)[(size_t)tpsTok(tp.tokenIdx) * a.H + col] =
-                ETr<ET>::fromf(v);
-          }
-        } else if constexpr (PHASE == 3) {
+        const int col0 = nBase + ni * 16;
+        // columns >= N are not written
+        const int nValid = FULL ? 4 : N - col0;
+        if (!FULL && nValid <= 0) continue;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          v[r] = accv[mi][ni][r] + bv[ni][r];
+          if constexpr (PHASE == 0)
+            v[r] = (act == 0)
+                ? fmaxf(v[r], 0.0f)
+                : 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752f));
+          if constexpr (PHASE == 1)
+            if (slot) v[r] = v[r] * rowScale;
+        }
+        if constexpr (PHASE == 3) {
           // gate logits, fp32; atomic accumulate when the fused gate
           // K-splits the logits GEMM over jobs (logits32 kept zero
           // between forwards by the route's re-zeroing pass)
-          if (a.atomicLogits)
-            atomicAdd(&reinterpret_cast<float*>(a.out)[(size_t)m * N + col], v);
-          else
-            reinterpret_cast<float*>(a.out)[(size_t)m * N + col] = v;
+          if (a.atomicLogits) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (r < nValid) atomicAdd(orow + col0 + r, v[r]);
+          } else if (FULL || (vecOK && nValid >= 4)) {
+            *reinterpret_cast<f32x4*>(orow + col0) =
+                f32x4{v[0], v[1], v[2], v[3]};
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (r < nValid) orow[col0 + r] = v[r];
+          }
         } else {
-          reinterpret_cast<ET*>(a.out)[(size_t)e * a.strideOExpert +
-                                       (size_t)m * N + col] =
-              ETr<ET>::fromf(v);
+          // PHASE 0 / PHASE 1 carry the sc1 policy (in-launch consumers
+          // in the fused kernel); PHASE 2 is always a plain store
+          storeRow4<SC1 && (PHASE == 0 || PHASE == 1)>(orow + col0, v,
+                                                        nValid, FULL || vecOK);
         }
       }
     }
+  };
+  constexpr bool CAN_SC1 = RT_SC1 && (PHASE == 0 || PHASE == 1);
+  const bool sc1 = CAN_SC1 && a.sc1Out != 0;
+  if (sc1 && fullN) epilogue(BoolC<CAN_SC1>{}, BoolC<true>{});
+  else if (sc1) epilogue(BoolC<CAN_SC1>{}, BoolC<false>{});
+  else if (fullN) epilogue(BoolC<false>{}, BoolC<true>{});
+  else epilogue(BoolC<false>{}, BoolC<false>{});
+  FM_STAMP(3);
+#ifdef FM_GEMM_STAMPS
+  {
+    const int blk =
+        blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+    if (tid == 0 && blk < FM_STAMP_BLOCKS && jobLocal < FM_STAMP_JOBS)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        g_gemmStamps[PHASE][blk][jobLocal][i] = fmStamp[i];
   }
+#endif
   return true;
 }
 
@@ -1090,11 +1288,9 @@ __device__ __forceinline__ bool gemm_job_body(
 template <typename ET, int PHASE, int ACT, bool HAS_BIAS, int BN, int BM = 256,
           typename WET = ET, int STAGES = 2>
 __global__ __launch_bounds__(512, 2) void k_group_gemm_bf16_big(GemmArgs a) {
-  constexpr int BK = 64;
   constexpr int BEZ = (int)sizeof(WET);
-  constexpr int SE = gemm_se<BM, BN, BEZ, STAGES>();
   __shared__ __attribute__((aligned(16))) char smem[
-      SE * BM * BK * 2 + SE * BN * BK * BEZ + BM * 8 + 16];
+      gemm_lds_bytes<BM, BN, BEZ, STAGES>()];
 
   // XCD-aware block remap (perf only, placement-independent for
   // correctness): the dispatcher places linear block b on XCD b%8; the
@@ -1119,6 +1315,7 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_bf16_big(GemmArgs a) {
   // several tiles instead of being paid once per 16-tile block
   // (mfma_probe: the identical tile loop runs 52.5 us/forward-equiv
   // persistent vs 71.4 us launched per-tile at the cfg2 up shape)
+  int par = 0;  // metadata copy; flips after every job that ran
   for (int jl = lin0; jl < nBlocks; jl += gstride) {
     const int xcd = jl % 8, pos = jl / 8;
     const int swz = a.noRemap
@@ -1128,8 +1325,10 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_bf16_big(GemmArgs a) {
     const int e = eEff % zE;
     const int ksplit = eEff / zE;
     const int rem = swz % (mT * nT);
-    (void)gemm_job_body<ET, PHASE, BN, BM, WET, STAGES>(
-        a, smem, e, ksplit, (rem % mT) * BM, (rem / mT) * BN, ACT, HAS_BIAS);
+    const bool ran = gemm_job_body<ET, PHASE, BN, BM, WET, STAGES>(
+        a, smem, e, ksplit, (rem % mT) * BM, (rem / mT) * BN, ACT, HAS_BIAS,
+        par, (jl - lin0) / gstride);
+    par ^= ran ? 1 : 0;
   }
 }
 
@@ -2135,14 +2334,18 @@ __device__ __forceinline__ void gemm_phase_walk(const GemmArgs& a, char* smem,
                                                 uint32_t* rowDone,
                                                 int debugBits) {
   const int qx = nJobs / 8, rx = nJobs % 8;
+  int par = 0;  // gemm_job_body metadata copy; flips after a job that ran
   for (int jl = blockIdx.x; jl < nJobs; jl += nBlocks) {
     const int xcd = jl % 8, pos = jl / 8;
     const int swz =
         (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
     const int e = swz / (mT * nT);
     const int rem = swz % (mT * nT);
-    const bool ran = gemm_job_body<ET, PHASE, BN, BM, WET, STAGES, CK, CN>(
-        a, smem, e, 0, (rem % mT) * BM, (rem / mT) * BN, act, hasBias != 0);
+    const bool ran =
+        gemm_job_body<ET, PHASE, BN, BM, WET, STAGES, CK, CN, true>(
+            a, smem, e, 0, (rem % mT) * BM, (rem / mT) * BN, act,
+            hasBias != 0, par);
+    par ^= ran ? 1 : 0;
     // job-count arrival: the epilogue's sc1 write-through stores need
     // only a per-wave drain before the relaxed arrival (Guideline 16
     // R1) - no cache-flushing release fence per block. Row arrivals
@@ -2170,6 +2373,7 @@ __device__ __forceinline__ void gemm_phase_walk_dn(
     const GemmArgs& a, const FusedMeta& f, char* smem, int mT, int nT,
     int nJobs, int nBlocks, int hasBias, uint32_t* doneCtr) {
   const int qx = nJobs / 8, rx = nJobs % 8;
+  int par = 0;  // as in gemm_phase_walk
   for (int jl = blockIdx.x; jl < nJobs; jl += nBlocks) {
     const int xcd = jl % 8, pos = jl / 8;
     const int swz =
@@ -2207,8 +2411,9 @@ __device__ __forceinline__ void gemm_phase_walk_dn(
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       }
       __syncthreads();
-      ran = gemm_job_body<ET, 1, BN, BM, WET, STAGES, CK, CN>(
-          a, smem, e, 0, m0, (rem / mT) * BN, 0, hasBias != 0);
+      ran = gemm_job_body<ET, 1, BN, BM, WET, STAGES, CK, CN, true>(
+          a, smem, e, 0, m0, (rem / mT) * BN, 0, hasBias != 0, par);
+      par ^= ran ? 1 : 0;
     }
     if (ran && !(f.debugBits & 1)) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2238,9 +2443,10 @@ __global__ __launch_bounds__(512, 1) void k_moe_fused(GemmArgs gl, GemmArgs gu,
     const int rest = j / f.nTiles;
     const int ks = rest % f.lgKS;
     const int nt = rest / f.lgKS;
+    // (block barriers follow every logits job: metadata copy 0 is free)
     (void)gemm_job_body<ET, 3, 128, 128, ET, 2, CH, 0>(gl, smem, 0, ks,
                                                         t * 128, nt * 128, 0,
-                                                        false);
+                                                        false, 0);
     // arrive on the tile: the logits writes are fp32 atomicAdds
     // (globally coherent), so only a vmcnt drain orders them before
     // the arrival; no cache release is needed
@@ -2595,9 +2801,9 @@ static int fusedPoisonCheck() {
 // host mirror of gemm_lds_bytes<> for the dynamic arena
 static int gemmLdsBytesRT(int BM, int BN, int BEZ, int stages) {
   const int SE = (stages == 3 && 3 * BM * 64 * 2 + 3 * BN * 64 * BEZ +
-                                      BM * 8 + 16 > 160 * 1024)
+                                      gemm_meta_bytes(BM) > 160 * 1024)
                      ? 2 : stages;
-  return SE * BM * 64 * 2 + SE * BN * 64 * BEZ + BM * 8 + 16;
+  return SE * BM * 64 * 2 + SE * BN * 64 * BEZ + gemm_meta_bytes(BM);
 }
 
 static void fusedGeoDims(int gm, int& bm, int& bn, int& stages) {
@@ -3153,9 +3359,16 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
       const char* e = getenv("FM_PERSIST");
       return !(e && e[0] == '0');
     }();
+    // FM_PERSIST_BLOCKS=<n> caps the persistent grid at n blocks (test
+    // knob: one block then walks many jobs at a small shape)
+    static const int persistCap = [] {
+      const char* e = getenv("FM_PERSIST_BLOCKS");
+      return e ? atoi(e) : 0;
+    }();
     if (persist && mode != 2) {
       const int jm = grid.x, jn = grid.y, J = jm * jn * nE * skf;
-      const int resident = (mode == 4) ? 512 : 256;
+      int resident = (mode == 4) ? 512 : 256;
+      if (persistCap > 0) resident = std::min(resident, persistCap);
       if (J > resident) {
         aa.totalJobs = J;
         aa.jobsMT = jm;
@@ -4127,4 +4340,17 @@ int fm_debug_mfma(void* stream, const void* A, const void* B, void* D) {
   return FM_OK;
 }
 
+#ifdef FM_GEMM_STAMPS
+// measurement build only: copy the phase stamps out (dst holds
+// 4 x 512 x 4 x 4 uint64) and zero them for the next forward
+int fm_debug_gemm_stamps(void* dst) {
+  FM_HIP_CHECK(hipDeviceSynchronize());
+  FM_HIP_CHECK(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_gemmStamps),
+                                   sizeof(g_gemmStamps)));
+  void* p = nullptr;
+  FM_HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_gemmStamps)));
+  FM_HIP_CHECK(hipMemset(p, 0, sizeof(g_gemmStamps)));
+  return FM_OK;
+}
+#endif
 }  // extern "C"
