@@ -43,6 +43,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_get_compiled_config.restype = ctypes.c_int
     lib.fm_get_num_local_experts.argtypes = []
     lib.fm_get_num_local_experts.restype = ctypes.c_int
+    lib.fm_last_forward_fused.argtypes = []
+    lib.fm_last_forward_fused.restype = ctypes.c_int
     lib.fm_moe_forward.argtypes = [p, p, p, p, p, p, p, p, i64]
     lib.fm_moe_forward.restype = ctypes.c_int
     lib.fm_moe_forward_phased.argtypes = [p, p, p, p, p, p, p, p, i64,

@@ -46,6 +46,18 @@ def element_size_of(code: int) -> int:
     return {0: 4, 1: 4, 2: 2, 3: 2, 4: 2, 5: 2}[code]
 
 
+# hidden_act enum (schema): 0 relu, 1 exact-erf gelu, 2 SwiGLU, 3 GeGLU.
+# 2/3 are GATED experts: h = act(x.Wglu^T) * (x.Wup^T), and the expert
+# weights carry a third [P, H] slab (slot 2 = Wglu): [nLx, 3, P, H].
+def is_gated(hidden_act: int) -> bool:
+    return hidden_act in (2, 3)
+
+
+def expert_mats(hidden_act: int) -> int:
+    """[P, H] slabs per expert in the expert-weights tensor (dim 1)."""
+    return 3 if is_gated(hidden_act) else 2
+
+
 def load_config(path: str | None = None) -> dict:
     path = path or DEFAULT_CONFIG_PATH
     with open(path) as f:
@@ -57,4 +69,13 @@ def load_config(path: str | None = None) -> dict:
         raise ValueError("sequence_len must be a multiple of 128 (schema)")
     if cfg["hidden_size"] % 64 or cfg["intermediate_size"] % 64:
         raise ValueError("hidden_size/intermediate_size must be multiples of 64 (schema)")
+    if cfg["hidden_act"] not in (0, 1, 2, 3):
+        raise ValueError(
+            f"hidden_act must be 0 (relu), 1 (gelu), 2 (swiglu) or 3 (geglu); "
+            f"got {cfg['hidden_act']}")
+    if is_gated(cfg["hidden_act"]) and cfg["torch_dtype"] == 5:
+        raise ValueError(
+            f"hidden_act={cfg['hidden_act']} (gated) is not supported with "
+            "torch_dtype=5 (MX fp8): the MX up epilogue cannot yet halve its "
+            "output width")
     return cfg

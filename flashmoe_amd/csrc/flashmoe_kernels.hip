@@ -509,7 +509,7 @@ struct GemmArgs {
   const TPS* tokenIds;  // [E,pEC] (this expert's row = tokenIds + e*pEC)
   const uint32_t* eC;
   long long strideAExpert;  // elements between experts in A (phase1: pEC*K)
-  long long strideBExpert;  // elements between experts in B (2*P*H)
+  long long strideBExpert;  // elements between experts in B (wMats*P*H)
   long long strideOExpert;  // elements between experts in out
   int K;                // reduction dim
   int N;                // output dim
@@ -547,7 +547,22 @@ struct GemmArgs {
                              // -> e4m3) and store fp8 + E8M0 scales
                              // directly - skips the k_quant_mx pass and
                              // the bf16 xM round-trip entirely
+  long long gluOffset;       // gated PHASE 0 (hidden_act 2/3): elements from
+                             // an expert's Wup (slot 0, at B) to its gating
+                             // projection Wglu (slot 2); N is then the
+                             // EFFECTIVE width 2P and the output pitch N/2
 };
+
+// Gated experts (hidden_act 2 SwiGLU, 3 GeGLU): h = act(g) * u with
+// g = x.Wglu^T, u = x.Wup^T, both still fp32 accumulators. The up GEMM
+// runs over an effective N = 2P whose tile-local B rows are sourced
+// INTERLEAVED from the two projections (16-row fragments in the MFMA
+// kernels, single rows in the fp32 kernel), so g and u of one output
+// element always sit in the same thread.
+__device__ __forceinline__ float gate_act(float v, int act) {
+  return act == 2 ? v / (1.0f + expf(-v))
+                  : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+}
 
 // address-space helpers for global_load_lds (direct HBM->LDS DMA)
 typedef __attribute__((address_space(1))) const uint32_t gas_u32;
@@ -557,6 +572,7 @@ template <typename ET, int PHASE, int ACT, bool HAS_BIAS, typename WET = ET>
 __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
   using vec8 = typename ETr<ET>::vec8;
   constexpr int BM = 128, BN = 128, BK = 64;
+  constexpr bool GATED = (PHASE == 0) && (ACT >= 2);
   // WET is the WEIGHT (B operand) storage element: == ET normally, or
   // fp8e4m3 for the config-5 fp8-weight path (W8A16: B staged through
   // glds as raw fp8 bytes, dequantized to bf16 at fragment-read time so
@@ -656,8 +672,16 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
     for (int i = 0; i < BGW; ++i) {
       const int grp = wave * BGW + i;
       const int row = grp * (1024 / (BK * BEZ)) + bgrow;
-      const int brow = min(n0 + row, N - 1);
-      const WET* bsrc = Bg + (size_t)brow * K + kt + bsc * (16 / BEZ);
+      int brow = min(n0 + row, N - 1);
+      const WET* bexp = Bg;
+      if constexpr (GATED) {
+        // fragment-interleaved source: even 16-row fragments read Wglu,
+        // odd ones Wup, same P rows; clamp per half (N is 2P here)
+        const int f = row >> 4;
+        brow = min((n0 >> 1) + (f >> 1) * 16 + (row & 15), (N >> 1) - 1);
+        if ((f & 1) == 0) bexp += a.gluOffset;
+      }
+      const WET* bsrc = bexp + (size_t)brow * K + kt + bsc * (16 / BEZ);
       __builtin_amdgcn_global_load_lds(
           (gas_u32*)bsrc, (las_u32*)((char*)Blds + grp * 1024), 16, 0, 0);
     }
@@ -743,6 +767,20 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
       if ((uint32_t)m >= routed) continue;
       const TPS tp = sTps[row];
       const float rowScale = multi ? sScale[row] : 1.0f;
+      if constexpr (GATED) {
+        // fragment pairs (2j, 2j+1) hold (g, u) of the same (row, p)
+        const int P = N >> 1;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int col = (n0 >> 1) + wc * 32 + j * 16 + cl;
+          if (col >= P) continue;
+          reinterpret_cast<ET*>(a.out)[(size_t)e * a.strideOExpert +
+                                       (size_t)m * P + col] =
+              ETr<ET>::fromf(gate_act(accv[mi][2 * j][r], ACT) *
+                             accv[mi][2 * j + 1][r]);
+        }
+        continue;
+      }
 #pragma unroll
       for (int ni = 0; ni < 4; ++ni) {
         const int col = n0 + wc * 64 + ni * 16 + cl;
@@ -870,7 +908,7 @@ __device__ __forceinline__ void storeRow4(ET* p, const float (&v)[4],
 // Only the fused kernel has in-launch consumers, so only its walks
 // instantiate the sc1 epilogues; the classic kernels compile them out.
 template <typename ET, int PHASE, int BN, int BM, typename WET, int STAGES,
-          int CK = 0, int CN = 0, bool RT_SC1 = false>
+          int CK = 0, int CN = 0, bool RT_SC1 = false, bool GATED = false>
 __device__ __forceinline__ bool gemm_job_body(
     const GemmArgs& a, char* smemBase, int e, int ksplit, int m0, int n0,
     int act, bool hasBias, int par, int jobLocal = 0) {
@@ -962,7 +1000,23 @@ __device__ __forceinline__ bool gemm_job_body(
 #pragma unroll
   for (int i = 0; i < GPW_B; ++i) {
     const int row = (wave * GPW_B + i) * (1024 / (BK * BEZ)) + bgrow;
-    bSrc[i] = Bg + (size_t)min(n0 + row, N - 1) * K + kStart + bsc * (16 / BEZ);
+    if constexpr (GATED) {
+      // Fragment-interleaved source (N is the effective 2P): tile-local
+      // row R lies in 16-row fragment f = R / 16; even f reads Wglu, odd f
+      // reads Wup, both at P row n0/2 + (f/2)*16 + R%16, clamped per half.
+      // A 1 KiB group covers 8 or 16 rows, so it never straddles a
+      // fragment. A wave's fragments start at an even f (NF is even), so
+      // accv[mi][2j] / accv[mi][2j+1] are g / u of the same (row, p).
+      static_assert(PHASE == 0, "gated epilogue is the up phase only");
+      const int f = row >> 4;
+      const int prow =
+          min((n0 >> 1) + (f >> 1) * 16 + (row & 15), (N >> 1) - 1);
+      bSrc[i] = Bg + ((f & 1) ? 0 : a.gluOffset) + (size_t)prow * K + kStart +
+                bsc * (16 / BEZ);
+    } else {
+      bSrc[i] =
+          Bg + (size_t)min(n0 + row, N - 1) * K + kStart + bsc * (16 / BEZ);
+    }
   }
 
   auto stageA = [&](int kt, int buf) {
@@ -1180,7 +1234,7 @@ __device__ __forceinline__ bool gemm_job_body(
     rowPitch = N;
   } else {
     outBase = reinterpret_cast<OT*>(a.out) + (size_t)e * a.strideOExpert;
-    rowPitch = N;
+    rowPitch = GATED ? (N >> 1) : N;  // gated: xM is [pEC, P], N is 2P
   }
   const bool vecOK =
       (rowPitch & 3) == 0 &&
@@ -1217,6 +1271,26 @@ __device__ __forceinline__ bool gemm_job_body(
         }
       } else {
         orow = outBase + (size_t)m * rowPitch;
+      }
+      if constexpr (GATED) {
+        // fragment pairs: accv[mi][2j] is g and accv[mi][2j+1] is u for
+        // P columns col0..col0+3; act(g) * u in fp32, rounded once by the
+        // store. The tile covers BN/2 P-columns from n0/2; a tile that is
+        // full in the effective N is full in P too.
+        const int P = N >> 1;
+        const int pBase = (n0 >> 1) + wc * (BN / 8) + cq;
+#pragma unroll
+        for (int j = 0; j < NF / 2; ++j) {
+          const int col0 = pBase + j * 16;
+          const int nValid = FULL ? 4 : P - col0;
+          if (!FULL && nValid <= 0) continue;
+          float v[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            v[r] = gate_act(accv[mi][2 * j][r], act) * accv[mi][2 * j + 1][r];
+          storeRow4<SC1>(orow + col0, v, nValid, FULL || vecOK);
+        }
+        continue;
       }
 #pragma unroll
       for (int ni = 0; ni < NF; ++ni) {
@@ -1325,7 +1399,10 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_bf16_big(GemmArgs a) {
     const int e = eEff % zE;
     const int ksplit = eEff / zE;
     const int rem = swz % (mT * nT);
-    const bool ran = gemm_job_body<ET, PHASE, BN, BM, WET, STAGES>(
+    // ACT 2/3 (PHASE 0 only) select the gated body; every other
+    // instantiation is the ungated code unchanged
+    const bool ran = gemm_job_body<ET, PHASE, BN, BM, WET, STAGES, 0, 0, false,
+                                   (PHASE == 0 && ACT >= 2)>(
         a, smem, e, ksplit, (rem % mT) * BM, (rem / mT) * BN, ACT, HAS_BIAS,
         par, (jl - lin0) / gstride);
     par ^= ran ? 1 : 0;
@@ -1704,6 +1781,7 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_mx(GemmArgs a) {
 template <int PHASE, int ACT, bool HAS_BIAS>
 __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
   constexpr int BM = 64, BN = 64, BK = 16;
+  constexpr bool GATED = (PHASE == 0) && (ACT >= 2);
   constexpr int LDT = BK + 1;
   __shared__ float Alds[BM * LDT];
   __shared__ float Blds[BN * LDT];
@@ -1747,8 +1825,16 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
           ? Ag + (size_t)tpsTok(sTps[row].tokenIdx) * a.H + kt + cc
           : Ag + (size_t)e * a.strideAExpert + (size_t)(m0 + row) * K + kt + cc;
       Alds[row * LDT + cc] = *src;
-      const int brow = min(n0 + row, N - 1);
-      Blds[row * LDT + cc] = Bg[(size_t)brow * K + kt + cc];
+      if constexpr (GATED) {
+        // row-interleaved source: even tile rows read Wglu, odd ones Wup,
+        // at P row (n0 + row) / 2; clamp per half (N is 2P here)
+        const int prow = min((n0 + row) >> 1, (N >> 1) - 1);
+        const float* bexp = (row & 1) ? Bg : Bg + a.gluOffset;
+        Blds[row * LDT + cc] = bexp[(size_t)prow * K + kt + cc];
+      } else {
+        const int brow = min(n0 + row, N - 1);
+        Blds[row * LDT + cc] = Bg[(size_t)brow * K + kt + cc];
+      }
     }
     __syncthreads();
 #pragma unroll
@@ -1788,6 +1874,19 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
       rowScale = reinterpret_cast<const float*>(
                      a.gate_out)[(size_t)tpsTok(tp.tokenIdx) * a.PX +
                                  a.expertOffset + e] / tp.probSum;
+    if constexpr (GATED) {
+      // column pairs (2j, 2j+1) hold (g, u) of the same (row, p)
+      const int P = N >> 1;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = ((n0 + tc) >> 1) + j;
+        if (col >= P) continue;
+        reinterpret_cast<float*>(a.out)[(size_t)e * a.strideOExpert +
+                                        (size_t)m * P + col] =
+            gate_act(acc[i][2 * j], ACT) * acc[i][2 * j + 1];
+      }
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int col = n0 + tc + j;
@@ -2579,6 +2678,9 @@ struct State {
   int S = 0, H = 0, P = 0, E = 0, PX = 0, nLx = 0, EC = 0, pEC = 0;
   size_t esz = 0;
   size_t wesz = 0;  // expert-weight element size (1 for fp8 weights)
+  int wMats = 2;    // [P,H] slabs per expert: 2 (up, down), or 3 for gated
+                    // experts (hidden_act 2/3: up, down, gating projection)
+  bool gated = false;
   // workspace
   TPS* tokenIds = nullptr;   // [E, pEC]
   uint32_t* eC = nullptr;    // [E]
@@ -2970,7 +3072,7 @@ static int moe_forward_fused(hipStream_t st, const void* x, const void* gate_w,
   gu.tokenIds = g.tokenIds;
   gu.eC = nullptr;  // set to the ctl-embedded eC mirror below
   gu.strideAExpert = 0;
-  gu.strideBExpert = 2LL * g.P * g.H;
+  gu.strideBExpert = (long long)g.wMats * g.P * g.H;
   gu.strideOExpert = (long long)g.pEC * g.P;
   gu.K = g.H;
   gu.N = g.P;
@@ -3096,6 +3198,18 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
              return FM_ERR_UNSUPPORTED;
   }
   g.wesz = (cfg->dtype == 4 || cfg->dtype == 5) ? 1 : g.esz;
+  if (cfg->hidden_act < 0 || cfg->hidden_act > 3) {
+    setErr("hidden_act must be 0 (relu), 1 (gelu), 2 (swiglu) or 3 (geglu)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  g.gated = cfg->hidden_act >= 2;
+  g.wMats = g.gated ? 3 : 2;
+  if (g.gated && cfg->dtype == 5) {
+    // the MX up epilogue quantizes 64-column blocks in-register; halving
+    // the output width there is separate work (open items)
+    setErr("gated hidden_act (2/3) is not supported with torch_dtype 5 (MX)");
+    return FM_ERR_UNSUPPORTED;
+  }
   if (cfg->dtype == 5 && (cfg->hidden_size % 128 || cfg->intermediate_size % 128)) {
     setErr("dtype 5 (MX fp8) requires H, P multiples of 128 (BK=128)");
     return FM_ERR_SHAPE;
@@ -3221,11 +3335,27 @@ int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,
 
 int fm_get_num_local_experts(void) { return g.initialized ? g.nLx : -1; }
 
+int fm_last_forward_fused(void) {
+  return g.initialized ? (g.lastForwardFused ? 1 : 0) : -1;
+}
+
 static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
                              int M, int nE) {
-  const bool hasBias = a.bias != nullptr;
   const int act = (phase == 0) ? a.act : 0;
-  const int N = a.N;
+  // gated up phase (hidden_act 2/3; never dtype 5, fm_initialize refuses
+  // it): the callers describe the plain [P, H] problem; the kernels run
+  // it over the effective N = 2P (tile-local B rows interleaved from Wglu
+  // and Wup) and store P columns. Grid, job counts and the mode
+  // thresholds below all see the effective N.
+  const bool gated = act >= 2;
+  const bool hasBias = a.bias != nullptr;
+  if (gated && hasBias) {  // every up launch passes here
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  const int N = gated ? 2 * a.N : a.N;
+  // slot 0 (Wup, at B) -> slot 2 (Wglu), in weight elements
+  const long long gluOffset = gated ? 2LL * a.N * a.K : 0;
   if (g.cfg.dtype == 5 && phase != 3) {
     // MX fp8 grouped GEMM (the gate-logits GEMM stays bf16: gate_w is
     // Element-typed). 256x256 tile when the shape affords it (staging
@@ -3342,6 +3472,8 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
     else mode = 2;
     if (forceMode >= 0) mode = forceMode;
     GemmArgs aa = a;
+    aa.N = N;
+    aa.gluOffset = gluOffset;
     aa.splitK = skf;
     aa.noRemap = noRemap;
     aa.totalJobs = 0;
@@ -3487,7 +3619,11 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
       else if (g.cfg.dtype == 4) GG_ET(bf16, PH, AC, HB, fp8e4m3);            \
       else GG_ET(bf16, PH, AC, HB, bf16);                                     \
     } while (0)
-    switch (sel) {
+    // gated (phase 0, bias-free by contract): ACT 2 SwiGLU / 3 GeGLU
+    if (gated) {
+      if (act == 2) GG_CASE(0, 2, false);
+      else GG_CASE(0, 3, false);
+    } else switch (sel) {
       case 0: GG_CASE(0, 0, false); break;
       case 1: GG_CASE(0, 0, true); break;
       case 2: GG_CASE(0, 1, false); break;
@@ -3503,6 +3639,17 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
   } else {
     dim3 block(256);
     dim3 grid(DIVUP(M, 64), DIVUP(N, 64), nE);
+    if (gated) {
+      GemmArgs aa = a;
+      aa.N = N;
+      aa.gluOffset = gluOffset;
+      if (act == 2)
+        hipLaunchKernelGGL((k_group_gemm_f32<0, 2, false>), grid, block, 0, st, aa);
+      else
+        hipLaunchKernelGGL((k_group_gemm_f32<0, 3, false>), grid, block, 0, st, aa);
+      FM_HIP_CHECK(hipGetLastError());
+      return FM_OK;
+    }
     const int sel = phase * 4 + act * 2 + (hasBias ? 1 : 0);
     switch (sel) {
       case 0: hipLaunchKernelGGL((k_group_gemm_f32<0, 0, false>), grid, block, 0, st, a); break;
@@ -3566,7 +3713,14 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // fused single-launch path (the north-star structure); classic
   // multi-kernel path remains for fp32 and as FM_FUSED=0 fallback
   g.lastForwardFused = false;
-  if (fusedEnabled() && g.esz == 2 && g.world == 1 && g.cfg.dtype != 5) {
+  if (b_up && g.gated) {  // refuse before anything is enqueued
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  // gated experts never take the fused kernel: its down-walk arrival
+  // counts are keyed on the number of up N-tiles
+  if (fusedEnabled() && g.esz == 2 && g.world == 1 && g.cfg.dtype != 5 &&
+      !g.gated) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -3604,7 +3758,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   up.tokenIds = g.tokenIds;
   up.eC = g.eC;
   up.strideAExpert = 0;
-  up.strideBExpert = 2LL * g.P * g.H;
+  up.strideBExpert = (long long)g.wMats * g.P * g.H;
   up.strideOExpert = (long long)g.pEC * g.P;
   up.K = g.H; up.N = g.P;
   up.EC = g.EC; up.pEC = g.pEC; up.PX = g.PX;
@@ -3811,7 +3965,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   GemmArgs up{};
   up.A = rows;
   up.B = reinterpret_cast<const char*>(expert_w) +
-         (size_t)local_e * 2 * g.P * g.H * g.wesz;
+         (size_t)local_e * g.wMats * g.P * g.H * g.wesz;
   up.bias = b_up;
   up.out = g.xM;  // scratch [n_rows, P]
   up.tokenIds = nullptr; up.eC = nullptr;
@@ -3825,7 +3979,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   GemmArgs dn = up;
   dn.A = g.xM;
   dn.B = reinterpret_cast<const char*>(expert_w) +
-         ((size_t)local_e * 2 + 1) * g.P * g.H * g.wesz;
+         ((size_t)local_e * g.wMats + 1) * g.P * g.H * g.wesz;
   dn.bias = b_dn;
   dn.out = out_rows;
   dn.K = g.P; dn.N = g.H;
@@ -4071,7 +4225,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   up.tokenIds = nullptr;
   up.eC = nullptr;
   up.strideAExpert = (long long)g.EC * g.H;
-  up.strideBExpert = 2LL * g.P * g.H;
+  up.strideBExpert = (long long)g.wMats * g.P * g.H;
   up.strideOExpert = (long long)g.EC * g.P;
   up.K = g.H;
   up.N = g.P;

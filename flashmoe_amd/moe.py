@@ -9,8 +9,8 @@ import ctypes
 import os
 
 from . import _ext
-from .config import (element_size_of, load_config, torch_dtype_of,
-                     weight_dtype_of)
+from .config import (element_size_of, expert_mats, load_config,
+                     torch_dtype_of, weight_dtype_of)
 
 _state = {
     "initialized": False,
@@ -151,12 +151,19 @@ def _validate_forward_args(input, gate_weights, expert_weights):
         raise ValueError(
             f"Expert count mismatch. Expected {nLx} local experts, got {expert_weights.size(0)}"
         )
-    if expert_weights.size(1) != 2:
+    act = _state["cfg"]["hidden_act"]
+    nm = expert_mats(act)
+    if expert_weights.size(1) != nm:
+        if nm == 3:
+            raise ValueError(
+                f"Expert weights must have up, down and gating projections "
+                f"[nLx, 3, P, H] for the gated hidden_act={act}. Got dim 1 = "
+                f"{expert_weights.size(1)}")
         raise ValueError("Expert weights must have up and down projections [nLx, 2, P, H]")
     if expert_weights.size(2) != P or expert_weights.size(3) != H:
         raise ValueError(
-            f"Expert weights must be [*, 2, P={P}, H={H}]. Got "
-            f"[*, 2, {expert_weights.size(2)}, {expert_weights.size(3)}]"
+            f"Expert weights must be [*, {nm}, P={P}, H={H}]. Got "
+            f"[*, {nm}, {expert_weights.size(2)}, {expert_weights.size(3)}]"
         )
     expect_dtype = torch_dtype_of(_state["cfg"]["torch_dtype"])
     expect_wdtype = weight_dtype_of(_state["cfg"]["torch_dtype"])

@@ -21,7 +21,8 @@ def main():
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from flashmoe_amd import moe
-    from flashmoe_amd.config import torch_dtype_of, weight_dtype_of
+    from flashmoe_amd.config import (expert_mats, torch_dtype_of,
+                                     weight_dtype_of)
 
     moe.initialize(config_path, rank=rank, world_size=world_size)
     if world_size > 1:
@@ -49,7 +50,8 @@ def main():
     input_tensor = torch.randn(mini_batch, seq_len, H, dtype=dtype, device="cuda")
     gate_weights = torch.randn(H, E, dtype=dtype, device="cuda")
     expert_weights = torch.randn(
-        nLx, 2, inter, H, dtype=dtype, device="cuda").to(wdtype)
+        nLx, expert_mats(config["hidden_act"]), inter, H, dtype=dtype,
+        device="cuda").to(wdtype)
 
     print(f"Process {rank}: Calling moe_forward...", flush=True)
     output = moe.moe_forward(input_tensor, gate_weights, expert_weights)

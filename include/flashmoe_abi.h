@@ -38,13 +38,26 @@ extern "C" {
  * runtime-quantized fp8 activations (per-64-element E8M0 block scales)
  * on the CDNA4 scaled MFMA; weights are passed exactly as for dtype 4,
  * activation quantization is internal. dtype 5 requires H, P multiples
- * of 128. */
+ * of 128.
+ *
+ * hidden_act: 0 relu, 1 exact-erf gelu: z = act(x.Wup^T + b_up).Wdn^T + b_dn
+ * with expert weights [nLx, 2, P, H]. 2 SwiGLU (silu(v) = v / (1 + exp(-v)))
+ * and 3 GeGLU (exact-erf gelu) are GATED experts:
+ *   h = act(x.Wglu^T) * (x.Wup^T), z = h.Wdn^T + b_dn
+ * computed in fp32 from the fp32 accumulators and rounded once to Element.
+ * Gated expert weights are [nLx, 3, P, H]: slot 0 = Wup [P,H], slot 1 =
+ * the down buffer (flat, used as [H,P]) - both exactly as for the
+ * two-slab layout - and slot 2 = the gating projection Wglu [P,H]; the
+ * expert stride is 3*P*H. Unsupported with a gated hidden_act
+ * (FM_ERR_UNSUPPORTED): b_up != NULL (every entry point), and dtype 5
+ * (at fm_initialize). Gated forwards always run the multi-kernel path,
+ * never the single-launch fused kernel. */
 typedef struct fm_config {
   int32_t num_experts;
   int32_t expert_top_k;
   int32_t capacity_factor;
   int32_t drop_tokens;
-  int32_t hidden_act; /* 0 relu, 1 gelu */
+  int32_t hidden_act; /* 0 relu, 1 gelu, 2 swiglu, 3 geglu (see above) */
   int32_t hidden_size;        /* H */
   int32_t intermediate_size;  /* P */
   int32_t sequence_len;  /* sequence_len * mini_batch (= S, the token
@@ -75,6 +88,11 @@ int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,
 /* Replaces _C.get_num_local_experts (python_bindings.cu:185-189). */
 int fm_get_num_local_experts(void);
 
+/* 1 if the last fm_moe_forward / fm_moe_forward_phased ran the
+ * single-launch fused kernel, 0 if it ran the multi-kernel path, -1
+ * before fm_initialize. */
+int fm_last_forward_fused(void);
+
 /* THE hot path. Replaces _C.moe_forward (python_bindings.cu:17-151) for
  * the single-rank case: gate -> route -> expert FFN -> combine on this
  * rank's tokens against this rank's nLx experts (world 1: all E).
@@ -85,9 +103,10 @@ int fm_get_num_local_experts(void);
  *            used as a row-major [E,H] matrix - reference quirk,
  *            moe.cuh:107-109; see oracle/moe_oracle.py docstring)
  * expert_w:  [nLx, 2, P, H] Element ([e][0]=Wup [P,H]; [e][1] flat,
- *            used as [H,P] - moe.cuh:114-116)
+ *            used as [H,P] - moe.cuh:114-116); [nLx, 3, P, H] with
+ *            [e][2]=Wglu [P,H] when hidden_act is gated (2/3)
  * b_up/b_dn: [nLx, P] / [nLx, H] Element or NULL (reference zero-fills,
- *            python_bindings.cu:80-82)
+ *            python_bindings.cu:80-82); b_up must be NULL when gated
  * gate_out:  [S, PX] Element out (softmax probs, moe.cuh:128-131)
  * moe_out:   [S, H] Element out
  * S:         token count this call (validated against frozen config)
@@ -116,7 +135,9 @@ int fm_read_routing(void* stream, uint32_t* routed_counts /* [E] */,
 
 /* Expert FFN on pre-packed rows (identity gather): rows [n_rows, H]
  * belong to local expert `local_e`; writes z = (act(rows@WupT+b))@WdnT+b
- * to out_rows [n_rows, H] (processor.cuh:685-751). */
+ * to out_rows [n_rows, H] (processor.cuh:685-751). Gated configs: the
+ * gated h above, expert stride 3*P*H, b_up must be NULL (this holds for
+ * fm_expert_ffn_segments / fm_expert_ffn_grouped too). */
 int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
                   const void* b_up, const void* b_dn, void* out_rows,
                   int64_t n_rows, int32_t local_e);
