@@ -420,6 +420,298 @@ __global__ __launch_bounds__(512) void k_gate_route(
 }
 
 // ---------------------------------------------------------------------------
+// Single-launch deterministic gate (bf16/fp16, E <= 64, inference):
+// grid = (S/128 tiles) x (128/TB sub-blocks). Each sub-block computes the
+// logits of its TB tokens with MFMA over the WHOLE K = H (K split over
+// four waves in contiguous ranges that depend on H alone, partials summed
+// through LDS in wave order -> the logits are a pure function of the
+// inputs, no atomics), then softmax / top-k exactly as route_tile_core,
+// stores its gate_out rows and hands sel / mCw to the tile's LAST
+// arriving sub-block through global scratch (producer half of the
+// Guideline 16 hand-off in its write-through form, R1: the payload is
+// stored sc1 like storeElem's, so the ticket needs no cache-flushing
+// release fence - the fenced form measured 3.4 us slower per launch,
+// DESIGN.md par.5g). The last arriver places the tile's 128 x K
+// selections (ballot + prefix popcount per expert, token order inside the
+// tile, one fetch_add per expert between tiles - the k_gate_route
+// semantics). No block ever waits for another: no spin, no co-residency
+// requirement. All ticket words are left zero for the next launch.
+// ---------------------------------------------------------------------------
+
+// arrive on a ticket word: every wave drains its stores (write-through
+// payload) and returning atomics, then thread 0 takes the ticket; every
+// thread gets the ticket's prior value. When it equals lastVal the block
+// is the last arriver and thread 0 also issues the (single) agent-scope
+// acquire. Everything handed over through a ticket is either stored sc1
+// (sel, mCw) or an agent-scope atomic (eCacc).
+__device__ __forceinline__ uint32_t gate_arrive(uint32_t* ctr,
+                                                uint32_t lastVal,
+                                                uint32_t* sFlag) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t old = __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED,
+                                                __HIP_MEMORY_SCOPE_AGENT);
+    if (old == lastVal) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    *sFlag = old;
+  }
+  __syncthreads();
+  return *sFlag;
+}
+
+// U K-steps of 32: all U (1 + NE) fragment loads issue before the first
+// MFMA waits (the kernel is latency-bound, not issue-bound; at H = 1024 a
+// wave's whole K range is one trip of 8 - which measured the same as two
+// trips of 4)
+template <typename T, int NE, int U>
+__device__ __forceinline__ void gate_logits_trip(const T* __restrict__ xrow,
+                                                 const T* const (&wp)[NE],
+                                                 int s, f32x4 (&acc)[4]) {
+  using vec8 = typename ETr<T>::vec8;
+  vec8 xv[U], wv[U][NE];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    xv[u] = *reinterpret_cast<const vec8*>(xrow + (s + u) * 32);
+#pragma unroll
+    for (int f = 0; f < NE; ++f)
+      wv[u][f] = *reinterpret_cast<const vec8*>(wp[f] + (s + u) * 32);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int f = 0; f < NE; ++f)
+      acc[f] = ETr<T>::mfma(wv[u][f], xv[u], acc[f]);
+}
+
+// one wave's share of the logits: 16 token rows x (NE x 16) expert columns
+// over K steps [s0, s1) of 32. Operand fragments go straight from global
+// to registers (16 B per lane; no other wave shares them). Swapped
+// operands as in gemm_job_body: lane & 15 = token row, acc[f][0..3] =
+// expert columns 16 f + 4 (lane >> 4) + 0..3.
+template <typename T, int NE>
+__device__ __forceinline__ void gate_logits_wave(const T* __restrict__ xrow,
+                                                 const T* __restrict__ gate_w,
+                                                 int H, int E, int lane,
+                                                 int s0, int s1,
+                                                 f32x4 (&acc)[4]) {
+  const T* wp[NE];
+#pragma unroll
+  for (int f = 0; f < NE; ++f)
+    wp[f] = gate_w + (size_t)min(f * 16 + (lane & 15), E - 1) * H +
+            (lane >> 4) * 8;
+  int s = s0;
+  for (; s + 8 <= s1; s += 8) gate_logits_trip<T, NE, 8>(xrow, wp, s, acc);
+  if (s + 4 <= s1) { gate_logits_trip<T, NE, 4>(xrow, wp, s, acc); s += 4; }
+  for (; s < s1; ++s) gate_logits_trip<T, NE, 1>(xrow, wp, s, acc);
+}
+
+template <typename T, int K, int TB>
+__global__ __launch_bounds__(TB * 16) void k_gate_fused(
+    const T* __restrict__ x, const T* __restrict__ gate_w,
+    T* __restrict__ gate_out, uint16_t* gateSel, float* gateCw,
+    uint32_t* tilesDone, uint32_t* tileArrive, uint32_t* eCacc,
+    TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC,
+    uint8_t* __restrict__ kept, int H, int E, int PX, int EC, int pEC) {
+  constexpr int NT = TB * 16;    // threads
+  constexpr int NWV = NT / 64;   // waves: TB/16 row groups x 4 K ranges
+  constexpr int SUB = 128 / TB;  // sub-blocks per tile
+  constexpr int LDP = 68;        // partial row stride (16-B aligned rows)
+  constexpr int LDL = 65;        // logits row stride (E <= 64)
+  __shared__ __attribute__((aligned(16))) float part[NWV * 16 * LDP];
+  __shared__ float logits[TB * LDL];
+  __shared__ float sInv[TB], sMax[TB];
+  __shared__ __attribute__((aligned(16))) uint16_t sSel[128 * K];
+  __shared__ uint16_t sLoc[128 * K];
+  __shared__ float sCw[128];
+  __shared__ uint32_t cntH[2 * 64];
+  __shared__ uint32_t base[64];
+  __shared__ uint32_t sFlag[2];
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int tile = blockIdx.x / SUB;
+  const int m0 = blockIdx.x * TB;  // first token of this sub-block
+
+  // ---- logits: whole K inside the block -----------------------------
+  {
+    const int kSteps = H / 32;
+    const int spw = DIVUP(kSteps, 4);
+    const int ks = wave & 3, rg = wave >> 2;
+    const int s0 = min(ks * spw, kSteps);
+    const int s1 = min(s0 + spw, kSteps);
+    f32x4 acc[4];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const T* xrow =
+        x + (size_t)(m0 + rg * 16 + (lane & 15)) * H + (lane >> 4) * 8;
+    const int NEr = DIVUP(E, 16);
+    if (NEr == 1) gate_logits_wave<T, 1>(xrow, gate_w, H, E, lane, s0, s1, acc);
+    else if (NEr == 2) gate_logits_wave<T, 2>(xrow, gate_w, H, E, lane, s0, s1, acc);
+    else gate_logits_wave<T, 4>(xrow, gate_w, H, E, lane, s0, s1, acc);
+    float* prow = part + (wave * 16 + (lane & 15)) * LDP + (lane >> 4) * 4;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+      if (f < NEr) *reinterpret_cast<f32x4*>(prow + f * 16) = acc[f];
+  }
+  __syncthreads();
+  // fixed wave-order reduction of the four K-range partials
+  for (int i = tid; i < TB * E; i += NT) {
+    const int row = i / E, col = i % E;
+    const float* p = part + ((row >> 4) * 4 * 16 + (row & 15)) * LDP + col;
+    float v = p[0];
+    v += p[16 * LDP];
+    v += p[2 * 16 * LDP];
+    v += p[3 * 16 * LDP];
+    logits[row * LDL + col] = v;
+  }
+  __syncthreads();
+
+  // ---- softmax / top-k: four threads per token (route_tile_core) -----
+  if (tid < TB * 4) {
+    constexpr int SUBS = 4;
+    const int token = tid / SUBS;
+    const int sub = tid % SUBS;
+    const float* lrow = logits + token * LDL;
+    const int chunk = (E + SUBS - 1) / SUBS;
+    const int e0 = min(E, sub * chunk);
+    const int e1 = min(E, e0 + chunk);
+    float m = -INFINITY;
+    for (int e = e0; e < e1; ++e) m = fmaxf(m, lrow[e]);
+#pragma unroll
+    for (int off = 1; off < SUBS; off <<= 1)
+      m = fmaxf(m, __shfl_xor(m, off, SUBS));
+    float d = 0.0f;
+    for (int e = e0; e < e1; ++e) d += __expf(lrow[e] - m);
+#pragma unroll
+    for (int off = 1; off < SUBS; off <<= 1) d += __shfl_xor(d, off, SUBS);
+    const float inv_d = 1.0f / d;
+    if (sub == 0) {
+      sInv[token] = inv_d;
+      sMax[token] = m;
+    }
+    uint32_t takenM = 0u;  // chunk <= 16
+    float mCw = 0.0f;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      float lv = -INFINITY;
+      int li = E;  // sentinel sorts after every real index
+      for (int e = e0; e < e1; ++e) {
+        const bool tk = (takenM >> (e - e0)) & 1u;
+        if (!tk && lrow[e] > lv) { lv = lrow[e]; li = e; }
+      }
+#pragma unroll
+      for (int off = 1; off < SUBS; off <<= 1) {
+        const float ov = __shfl_xor(lv, off, SUBS);
+        const int oi = __shfl_xor(li, off, SUBS);
+        if (ov > lv || (ov == lv && oi < li)) { lv = ov; li = oi; }
+      }
+      if (li >= e0 && li < e1) takenM |= 1u << (li - e0);
+      if (sub == 0) {
+        __hip_atomic_store(gateSel + (size_t)(m0 + token) * K + i,
+                           (uint16_t)li, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        mCw += __expf(lv - m) * inv_d;
+      }
+    }
+    if (sub == 0)
+      __hip_atomic_store(gateCw + m0 + token, mCw, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // ---- arrive as soon as the hand-off payload is out: the gate_out rows
+  // below are not part of it, so they stay off the last arriver's critical
+  // path (the arrive's barriers also order sMax / sInv for them)
+  const bool lastOfTile =
+      gate_arrive(tileArrive + tile, SUB - 1, &sFlag[0]) == SUB - 1;
+  // coalesced gate_out rows [TB, PX], pad columns 0
+  for (int i = tid * 8; i < TB * PX; i += NT * 8) {
+    const int row = i / PX, col0 = i % PX;
+    const float mR = sMax[row], ivR = sInv[row];
+    const float* lrow = logits + row * LDL;
+    struct __attribute__((aligned(16))) V8 { T x[8]; } v;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int col = col0 + q;
+      const float pv = (col < E) ? __expf(lrow[col] - mR) * ivR : 0.0f;
+      fromF(pv, v.x[q]);
+    }
+    *reinterpret_cast<V8*>(gate_out + (size_t)(m0 + row) * PX + col0) = v;
+  }
+
+  if (!lastOfTile) return;  // everyone but the tile's last arriver is done
+
+  // ---- last arriver: place the tile's 128 x K selections -------------
+  // sel / mCw were produced in THIS launch by other CUs: agent-scope
+  // loads only (never a path the compiler may turn into a scalar-cache
+  // load - see gemm_job_body's eC comment)
+  const int t0 = tile * 128;
+  for (int i = tid; i < 128 * K; i += NT)
+    sSel[i] = __hip_atomic_load(gateSel + (size_t)t0 * K + i, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
+  for (int i = tid; i < 128; i += NT)
+    sCw[i] = __hip_atomic_load(gateCw + t0 + i, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  {
+    // a token's K selections are distinct experts, so an entry's index
+    // within the tile is the number of EARLIER tokens that selected the
+    // same expert: ballot + prefix popcount per 64-token half
+    const int half = wave & 1;
+    const int tok = half * 64 + lane;
+    uint16_t s[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) s[j] = sSel[tok * K + j];
+    for (int e = wave >> 1; e < E; e += NWV / 2) {
+      int hj = -1;
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        if (s[j] == (uint16_t)e) hj = j;
+      const unsigned long long mk = __ballot(hj >= 0);
+      const uint32_t pre = __builtin_amdgcn_mbcnt_hi(
+          (uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u));
+      if (hj >= 0) sLoc[tok * K + hj] = (uint16_t)pre;
+      if (lane == 0) cntH[half * 64 + e] = (uint32_t)__popcll(mk);
+    }
+  }
+  __syncthreads();
+  if (tid < E)
+    base[tid] = __hip_atomic_fetch_add(eCacc + tid, cntH[tid] + cntH[64 + tid],
+                                       __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  // ---- second ticket, taken as soon as this tile's counts are in eCacc
+  // (tokenIds / kept below have no reader inside this launch); the block
+  // completing it publishes the raw counts and re-zeroes the scratch
+  const uint32_t nTiles = gridDim.x / SUB;
+  if (gate_arrive(tilesDone, nTiles - 1, &sFlag[1]) == nTiles - 1) {
+    if (tid < E) {
+      eC[tid] = __hip_atomic_load(eCacc + tid, __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_AGENT);  // raw counts
+      __hip_atomic_store(eCacc + tid, 0u, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid == 0)
+      __hip_atomic_store(tilesDone, 0u, __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid == 0)
+    __hip_atomic_store(tileArrive + tile, 0u, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+  for (int i = tid; i < 128 * K; i += NT) {
+    const int tok = i / K, j = i % K;
+    const int e = sSel[i];
+    bool keep = false;
+    if (e < E) {  // e == E only when the token's logits are all NaN/-inf
+      const uint32_t slot =
+          base[e] + sLoc[i] + (tok >= 64 ? cntH[e] : 0u);
+      keep = slot < (uint32_t)EC;
+      if (keep)
+        tokenIds[(size_t)e * pEC + slot] =
+            TPS{(uint32_t)(t0 + tok) | ((uint32_t)j << 28), sCw[tok]};
+    }
+    if (kept) kept[(size_t)(t0 + tok) * K + j] = keep ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // MX-fp8 activation quantization (dtype 5, the cfg5 regime: "CDNA4 fp8
 // MFMA + token-scaling"): bf16 rows -> fp8 e4m3 bytes + per-64-element
 // E8M0 block scales. Block size 64 matches the EMPIRICAL scale
@@ -2687,6 +2979,11 @@ struct State {
   float* logits32 = nullptr; // [S, E] gate logit accumulator
   float* gML = nullptr;      // [E] training aux: mean gate prob
   float* gMeC = nullptr;     // [E] training aux: routed fraction
+  // single-launch gate (k_gate_fused): one allocation, 16-B aligned parts:
+  //   tilesDone + pad | tileArrive[S/128] | eCacc[E]   (zero after use)
+  //   | gateCw[S] f32 | gateSel[S, k] u16              (hand-off payload)
+  uint32_t* gateCtl = nullptr;
+  size_t gateArriveOff = 0, gateEcOff = 0, gateCwOff = 0, gateSelOff = 0;
   // one-sided P2P heap (opt-in EP transport)
   char* heap = nullptr;      // local block: recv | ret | dispFlags | retFlags
   size_t heapRecvOff = 0, heapRetOff = 0, heapDFlagOff = 0, heapRFlagOff = 0;
@@ -2764,8 +3061,61 @@ size_t gate_lds_bytes(int E, size_t esz) {
   return 128 * (E + 1) * sizeof(float) + (128 + E) * (64 + 8) * esz;
 }
 
+static bool gateFusedEnabled() {
+  // FM_GATE_FUSED=0 forces the two-kernel gate; default on. Re-read per
+  // call (tests toggle it) and part of the graph key, like FM_FUSED.
+  const char* e = getenv("FM_GATE_FUSED");
+  return !(e && e[0] == '0');
+}
+
+// does launch_gate take the single-launch k_gate_fused?
+static bool gateFusedApplies() {
+  return g.gateCtl && g.esz == 2 && g.E <= 64 && !g.cfg.is_training &&
+         gateFusedEnabled();
+}
+
+// sub-block token count of k_gate_fused (16 -> 256 threads, S/16 blocks;
+// 32 -> 512 threads, S/32 blocks)
+constexpr int kGateTB = 16;
+
+template <typename T>
+int launch_gate_fused(hipStream_t st, const void* x, const void* gate_w,
+                      void* gate_out, int64_t S) {
+  char* ws = reinterpret_cast<char*>(g.gateCtl);
+#define GATE_FUSED(KK)                                                        \
+  hipLaunchKernelGGL((k_gate_fused<T, KK, kGateTB>),                          \
+                     dim3((unsigned)(S / kGateTB)), dim3(kGateTB * 16), 0,    \
+                     st, reinterpret_cast<const T*>(x),                       \
+                     reinterpret_cast<const T*>(gate_w),                      \
+                     reinterpret_cast<T*>(gate_out),                          \
+                     reinterpret_cast<uint16_t*>(ws + g.gateSelOff),          \
+                     reinterpret_cast<float*>(ws + g.gateCwOff), g.gateCtl,   \
+                     reinterpret_cast<uint32_t*>(ws + g.gateArriveOff),       \
+                     reinterpret_cast<uint32_t*>(ws + g.gateEcOff),           \
+                     g.tokenIds, g.eC, g.kept, g.H, g.E, g.PX, g.EC, g.pEC)
+  switch (g.cfg.expert_top_k) {
+    case 1: GATE_FUSED(1); break;
+    case 2: GATE_FUSED(2); break;
+    case 3: GATE_FUSED(3); break;
+    case 4: GATE_FUSED(4); break;
+    case 5: GATE_FUSED(5); break;
+    case 6: GATE_FUSED(6); break;
+    case 7: GATE_FUSED(7); break;
+    case 8: GATE_FUSED(8); break;
+    default: setErr("unsupported expert_top_k (1..8)"); return FM_ERR_UNSUPPORTED;
+  }
+#undef GATE_FUSED
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
 int launch_gate(hipStream_t st, const void* x, const void* gate_w,
                 void* gate_out, int64_t S) {
+  // bf16/fp16, E <= 64, inference: one deterministic launch
+  if (gateFusedApplies())
+    return g.cfg.dtype == 3
+               ? launch_gate_fused<fp16>(st, x, gate_w, gate_out, S)
+               : launch_gate_fused<bf16>(st, x, gate_w, gate_out, S);
   // split gate: logits GEMM parallelised over (token tile, H chunk),
   // then per-tile softmax/top-k/route (see k_gate_logits/k_gate_route)
   const int tiles = (int)(S / 128);
@@ -3252,6 +3602,20 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   FM_HIP_CHECK(hipMalloc(&g.cbuf,
                          (size_t)g.S * g.cfg.expert_top_k * g.H * g.esz));
   FM_HIP_CHECK(hipMalloc(&g.kept, (size_t)g.S * g.cfg.expert_top_k));
+  if (g.esz == 2 && g.E <= 64 && !g.cfg.is_training) {
+    // k_gate_fused workspace; the ticket words are zeroed here once and
+    // left zero by every launch (no memset node per forward)
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    g.gateArriveOff = 16;
+    g.gateEcOff = g.gateArriveOff + up16((size_t)(g.S / 128) * sizeof(uint32_t));
+    g.gateCwOff = g.gateEcOff + up16((size_t)g.E * sizeof(uint32_t));
+    g.gateSelOff = g.gateCwOff + up16((size_t)g.S * sizeof(float));
+    const size_t bytes =
+        g.gateSelOff +
+        up16((size_t)g.S * g.cfg.expert_top_k * sizeof(uint16_t));
+    FM_HIP_CHECK(hipMalloc(&g.gateCtl, bytes));
+    FM_HIP_CHECK(hipMemset(g.gateCtl, 0, bytes));
+  }
   if (g.cfg.dtype == 5) {
     // sized for BOTH the single-rank forward (S rows) and the EP
     // segments path (up to nLxAlloc*pEC recv rows)
@@ -3303,6 +3667,7 @@ int fm_finalize(void) {
   (void)hipFree(g.O32);
   (void)hipFree(g.cbuf); (void)hipFree(g.kept);
   (void)hipFree(g.logits32); (void)hipFree(g.gML);
+  if (g.gateCtl) (void)hipFree(g.gateCtl);
   if (g.x8) { (void)hipFree(g.x8); (void)hipFree(g.xs);
               (void)hipFree(g.xM8); (void)hipFree(g.xMs); }
   if (g.fusedCtl) (void)hipFree(g.fusedCtl);
@@ -3728,7 +4093,8 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
       return rc;
     }
   }
-  // eC is zeroed by the gate logits kernel (block 0)
+  // eC is written by the gate itself (k_gate_fused publishes it whole;
+  // the two-kernel gate zeroes it in the logits kernel's block 0)
   // O32 is kept zero across calls (zeroed at initialize; k_cast_out
   // re-zeroes after reading)
   // k==1: zero moe_out so dropped tokens keep zeros (clearState,
@@ -3826,7 +4192,8 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                   const_cast<void*>(expert_w), const_cast<void*>(b_up),
                   const_cast<void*>(b_dn), gate_out, moe_out,
                   reinterpret_cast<void*>(static_cast<uintptr_t>(
-                      (uint64_t)S << 1 | (fusedEnabled() ? 1 : 0)))};
+                      (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
+                      (fusedEnabled() ? 1 : 0)))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;
     g.graphValid = false;  // replay failed: rebuild next time
