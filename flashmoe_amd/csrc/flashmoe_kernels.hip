@@ -505,6 +505,22 @@ __device__ __forceinline__ void gate_logits_wave(const T* __restrict__ xrow,
   for (; s < s1; ++s) gate_logits_trip<T, NE, 1>(xrow, wp, s, acc);
 }
 
+// -DFM_GEMM_STAMPS (measurement build only): thread 0 of every block of
+// k_gate_fused (slot 0) and k_cast_combine (slot 1) records the 100 MHz
+// wall clock at entry and exit, so tools/gemm_phase_stamps.py can lay the
+// four kernels of a forward on one timeline (see g_gemmStamps below).
+#ifdef FM_GEMM_STAMPS
+constexpr int FM_AUX_KERNELS = 2, FM_AUX_BLOCKS = 4096;
+__device__ unsigned long long g_auxStamps[FM_AUX_KERNELS][FM_AUX_BLOCKS][2];
+#define FM_AUX_STAMP(k, i)                                                    \
+  do {                                                                        \
+    if (threadIdx.x == 0 && blockIdx.x < FM_AUX_BLOCKS)                       \
+      g_auxStamps[k][blockIdx.x][i] = __builtin_amdgcn_s_memrealtime();       \
+  } while (0)
+#else
+#define FM_AUX_STAMP(k, i) do {} while (0)
+#endif
+
 template <typename T, int K, int TB>
 __global__ __launch_bounds__(TB * 16) void k_gate_fused(
     const T* __restrict__ x, const T* __restrict__ gate_w,
@@ -529,6 +545,7 @@ __global__ __launch_bounds__(TB * 16) void k_gate_fused(
 
   const int tid = threadIdx.x;
   const int wave = tid >> 6, lane = tid & 63;
+  FM_AUX_STAMP(0, 0);
   const int tile = blockIdx.x / SUB;
   const int m0 = blockIdx.x * TB;  // first token of this sub-block
 
@@ -637,7 +654,10 @@ __global__ __launch_bounds__(TB * 16) void k_gate_fused(
     *reinterpret_cast<V8*>(gate_out + (size_t)(m0 + row) * PX + col0) = v;
   }
 
-  if (!lastOfTile) return;  // everyone but the tile's last arriver is done
+  if (!lastOfTile) {  // everyone but the tile's last arriver is done
+    FM_AUX_STAMP(0, 1);
+    return;
+  }
 
   // ---- last arriver: place the tile's 128 x K selections -------------
   // sel / mCw were produced in THIS launch by other CUs: agent-scope
@@ -709,6 +729,7 @@ __global__ __launch_bounds__(TB * 16) void k_gate_fused(
     }
     if (kept) kept[(size_t)(t0 + tok) * K + j] = keep ? 1 : 0;
   }
+  FM_AUX_STAMP(0, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -1189,6 +1210,35 @@ __device__ __forceinline__ void storeRow4(ET* p, const float (&v)[4],
   }
 }
 
+// Eight consecutive output columns of one row from one lane, already
+// converted and packed two elements per dword (w[0] = columns 0-1 ..
+// w[3] = columns 6-7), nValid of them inside N. p is 16-byte aligned.
+// Wide path: ONE 16-byte store. A group that straddles N falls back to
+// 8-byte halves and then to elements, storing the same packed bits.
+template <typename ET>
+__device__ __forceinline__ void storeRow8(ET* p, const uint32_t (&w)[4],
+                                          int nValid) {
+  static_assert(sizeof(ET) == 2, "packed pairs of 2-byte elements");
+  if (nValid >= 8) {
+    *reinterpret_cast<u32x4*>(p) = u32x4{w[0], w[1], w[2], w[3]};
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int nv = nValid - 4 * h;
+      if (nv >= 4) {
+        *reinterpret_cast<uint64_t*>(p + 4 * h) =
+            (uint64_t)w[2 * h] | ((uint64_t)w[2 * h + 1] << 32);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (r < nv)
+            reinterpret_cast<uint16_t*>(p)[4 * h + r] =
+                (uint16_t)(w[2 * h + (r >> 1)] >> (16 * (r & 1)));
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // One (e, m0, n0, ksplit) tile job of the big-tile grouped GEMM: the
 // shared body of k_group_gemm_bf16_big (classic multi-kernel path) and
@@ -1531,11 +1581,20 @@ __device__ __forceinline__ bool gemm_job_body(
   const bool vecOK =
       (rowPitch & 3) == 0 &&
       (reinterpret_cast<uintptr_t>(outBase) & (4 * sizeof(OT) - 1)) == 0;
+  // 16-byte stores of eight 2-byte elements: every row base 16-byte aligned
+  const bool vec16OK =
+      (rowPitch & 7) == 0 && (reinterpret_cast<uintptr_t>(outBase) & 15) == 0;
+  // the 16-byte path exists where a (lane, mi) has a PAIR of packed
+  // 2-byte outputs (the gated BN=128 tile has one and keeps 8 bytes)
+  constexpr int NOUT = GATED ? NF / 2 : NF;  // packed outputs per mi
+  constexpr bool W16 = PHASE != 3 && NOUT >= 2;
 
   // interior tile (every column group wholly inside N, rows wide-
   // aligned): no column predicate at all. Ragged tiles take the checked
   // instantiation.
-  const bool fullN = vecOK && (n0 + BN <= N);
+  // (Where the 16-byte path exists an interior tile also needs 16-byte
+  // rows, so that instantiation holds the 16-byte stores alone.)
+  const bool fullN = vecOK && (!W16 || vec16OK) && (n0 + BN <= N);
 
   // one instantiation per cache policy and per interior/ragged: the sc1
   // (agent-scope write-through) choice and the column checks are ONE
@@ -1543,6 +1602,88 @@ __device__ __forceinline__ bool gemm_job_body(
   auto epilogue = [&](auto sc1c, auto fullc) {
     constexpr bool SC1 = decltype(sc1c)::value;
     constexpr bool FULL = decltype(fullc)::value;
+    // 16-byte stores. A lane holds columns cq..cq+3 of every fragment; a
+    // fragment pair (x, y) exchanges its packed dwords with
+    // v_permlane16_swap (x's odd 16-lane rows <-> y's even rows), after
+    // which 16-lane group g holds the EIGHT consecutive columns
+    // 8*(g>>1)..+7 of fragment x + (g&1): one 16-byte store per pair
+    // instead of two 8-byte ones. Values are converted before the swap,
+    // so the stored bits are those of the 8-byte path. Plain stores only:
+    // the sc1 word stays 8 bytes (the widest agent-scope write-through
+    // store), and a single packed output (gated BN=128) has no pair.
+    if constexpr (!SC1 && W16) {
+      if (FULL || vec16OK) {  // an interior tile implies vec16OK here
+        const int g4 = lane >> 4;
+        const int nOut = GATED ? (N >> 1) : N;
+        // first of this lane's eight columns in pair 0
+        const int col8 = (GATED ? (n0 >> 1) + wc * (BN / 8)
+                                : n0 + wc * (BN / 4)) +
+                         (g4 & 1) * 16 + (g4 >> 1) * 8;
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          const int row = wr * (BM / 2) + mi * 16 + rl16;
+          const int m = m0 + row;
+          OT* orow;
+          float rowScale = 1.0f;
+          if constexpr (PHASE == 1) {
+            const TPS tp = sTps[row];  // {0, 1.0f} for rows past routed
+            if (slot) {
+              orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * a.topk +
+                                tpsJ(tp.tokenIdx)) * rowPitch;
+              if (scaled) rowScale = sScale[row];
+            } else {
+              orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+            }
+          } else {
+            orow = outBase + (size_t)m * rowPitch;
+          }
+          uint32_t w[NOUT][2];
+#pragma unroll
+          for (int no = 0; no < NOUT; ++no) {
+            float v[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              if constexpr (GATED) {
+                v[r] = gate_act(accv[mi][2 * no][r], act) *
+                       accv[mi][2 * no + 1][r];
+              } else {
+                v[r] = accv[mi][no][r] + bv[no][r];
+                if constexpr (PHASE == 0)
+                  v[r] = (act == 0)
+                      ? fmaxf(v[r], 0.0f)
+                      : 0.5f * v[r] *
+                            (1.0f + erff(v[r] * 0.70710678118654752f));
+                if constexpr (PHASE == 1)
+                  if (slot) v[r] = v[r] * rowScale;
+              }
+            }
+            w[no][0] = ETr<ET>::pack2(v[0], v[1]);
+            w[no][1] = ETr<ET>::pack2(v[2], v[3]);
+          }
+          // the swaps run under full EXEC, ahead of the row predicate
+#pragma unroll
+          for (int no = 0; no < NOUT; no += 2)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const auto sw = __builtin_amdgcn_permlane16_swap(
+                  w[no][h], w[no + 1][h], false, false);
+              w[no][h] = sw[0];
+              w[no + 1][h] = sw[1];
+            }
+          if ((uint32_t)m >= routed) continue;  // rows past routed
+#pragma unroll
+          for (int no = 0; no < NOUT; no += 2) {
+            const int c = col8 + no * 16;
+            const int nValid = FULL ? 8 : nOut - c;  // columns >= N: not written
+            if (!FULL && nValid <= 0) continue;
+            const uint32_t ww[4] = {w[no][0], w[no][1], w[no + 1][0],
+                                    w[no + 1][1]};
+            storeRow8(orow + c, ww, nValid);
+          }
+        }
+        return;
+      }
+    }
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       const int row = wr * (BM / 2) + mi * 16 + rl16;
@@ -2207,19 +2348,31 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
 }
 
 // sum the k non-atomic combine slots (kept-masked) into the output
-// (k>1 path; replaces the fp32-atomic accumulator + cast). One block
-// per token chunk, 16-B vector loads per slot (a scalar grid-stride
+// (k>1 path; replaces the fp32-atomic accumulator + cast). Blocks walk
+// token groups, 16-B vector loads per slot (a scalar grid-stride
 // version with a per-element div ran at 1.35 TB/s on the cfg5 shape).
 template <typename T, int K>
 __global__ void k_cast_combine(const T* __restrict__ cbuf,
                                const uint8_t* __restrict__ kept,
                                T* __restrict__ out, int S, int H) {
   constexpr int EPU = 16 / sizeof(T);
-  for (int t = blockIdx.x; t < S; t += gridDim.x) {
+  FM_AUX_STAMP(1, 0);
+  // A token is H / EPU 16-byte chunks. With fewer chunks than threads
+  // the block covers tpb = blockDim / chunks tokens per iteration, one
+  // chunk per thread (the blockDim % chunks threads left over idle);
+  // otherwise one token per iteration, threads striding over its chunks.
+  // Either way every output element is one thread's sum over j in order.
+  const int cpt = max(1, H / EPU);
+  const int tpb = cpt < (int)blockDim.x ? (int)blockDim.x / cpt : 1;
+  const int tl = tpb > 1 ? (int)threadIdx.x / cpt : 0;
+  const int h0 = ((int)threadIdx.x - tl * cpt) * EPU;
+  const int hStep = tpb > 1 ? H : (int)blockDim.x * EPU;
+  for (int t = blockIdx.x * tpb + tl; t < S && tl < tpb;
+       t += gridDim.x * tpb) {
     bool kp[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) kp[j] = kept[(size_t)t * K + j] != 0;
-    for (int h = threadIdx.x * EPU; h < H; h += blockDim.x * EPU) {
+    for (int h = h0; h < H; h += hStep) {
       float acc[EPU];
 #pragma unroll
       for (int q = 0; q < EPU; ++q) acc[q] = 0.0f;
@@ -2253,6 +2406,7 @@ __global__ void k_cast_combine(const T* __restrict__ cbuf,
           *reinterpret_cast<const u32x4*>(ov);
     }
   }
+  FM_AUX_STAMP(1, 1);
 }
 
 // cast the fp32 combine accumulator into the Element output (k>1 path)
@@ -4034,7 +4188,10 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
 }
 
 static int launch_cast_combine(hipStream_t st, void* moe_out) {
-  const int blocks = std::min(g.S, 4096);
+  // tokens per block iteration (mirrors the kernel): H / (16 / esz) chunks
+  const int cpt = std::max(1, g.H / (16 / (int)g.esz));
+  const int tpb = cpt < 256 ? 256 / cpt : 1;
+  const int blocks = std::min(DIVUP(g.S, tpb), 4096);
 #define CC(T, KK)                                                             \
   hipLaunchKernelGGL((k_cast_combine<T, KK>), dim3(blocks), dim3(256), 0, st, \
                      reinterpret_cast<const T*>(g.cbuf), g.kept,              \
@@ -4871,6 +5028,17 @@ int fm_debug_gemm_stamps(void* dst) {
   void* p = nullptr;
   FM_HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_gemmStamps)));
   FM_HIP_CHECK(hipMemset(p, 0, sizeof(g_gemmStamps)));
+  return FM_OK;
+}
+// the same for the gate / combine entry-exit stamps (dst holds
+// 2 x 4096 x 2 uint64)
+int fm_debug_aux_stamps(void* dst) {
+  FM_HIP_CHECK(hipDeviceSynchronize());
+  FM_HIP_CHECK(hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_auxStamps),
+                                   sizeof(g_auxStamps)));
+  void* p = nullptr;
+  FM_HIP_CHECK(hipGetSymbolAddress(&p, HIP_SYMBOL(g_auxStamps)));
+  FM_HIP_CHECK(hipMemset(p, 0, sizeof(g_auxStamps)));
   return FM_OK;
 }
 #endif
