@@ -8,6 +8,7 @@ from .moe import (  # noqa: F401
     finalize,
     get_compiled_config,
     get_num_local_experts,
+    get_num_shared_experts,
     initialize,
     moe_forward,
 )
@@ -21,4 +22,5 @@ __all__ = [
     "finalize",
     "moe_forward",
     "get_num_local_experts",
+    "get_num_shared_experts",
 ]

@@ -29,6 +29,8 @@ class FMConfig(ctypes.Structure):
         ("mini_batch", ctypes.c_int32),
         ("dtype", ctypes.c_int32),
         ("is_training", ctypes.c_int32),
+        # last field; keyword construction without it leaves 0 (none)
+        ("num_shared_experts", ctypes.c_int32),
     ]
 
 
@@ -43,6 +45,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_get_compiled_config.restype = ctypes.c_int
     lib.fm_get_num_local_experts.argtypes = []
     lib.fm_get_num_local_experts.restype = ctypes.c_int
+    lib.fm_get_num_shared_experts.argtypes = []
+    lib.fm_get_num_shared_experts.restype = ctypes.c_int
     lib.fm_last_forward_fused.argtypes = []
     lib.fm_last_forward_fused.restype = ctypes.c_int
     lib.fm_moe_forward.argtypes = [p, p, p, p, p, p, p, p, i64]

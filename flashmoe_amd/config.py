@@ -58,6 +58,19 @@ def expert_mats(hidden_act: int) -> int:
     return 3 if is_gated(hidden_act) else 2
 
 
+# num_shared_experts (optional key, default 0): FFNs applied to EVERY token,
+# unrouted and unscaled, and added to the routed result (DeepSeek-MoE /
+# Qwen-MoE shared experts). Their slabs trail the routed ones:
+# expert weights are [nLx + nSh, mats, P, H].
+MAX_SHARED_EXPERTS = 4
+MAX_COMBINE_SLOTS = 16  # the combine slot index j has four bits
+
+
+def num_shared(cfg: dict) -> int:
+    """Shared experts of a config (0 when the key is absent)."""
+    return int(cfg.get("num_shared_experts", 0))
+
+
 def load_config(path: str | None = None) -> dict:
     path = path or DEFAULT_CONFIG_PATH
     with open(path) as f:
@@ -73,6 +86,21 @@ def load_config(path: str | None = None) -> dict:
         raise ValueError(
             f"hidden_act must be 0 (relu), 1 (gelu), 2 (swiglu) or 3 (geglu); "
             f"got {cfg['hidden_act']}")
+    nsh = cfg.get("num_shared_experts", 0)
+    if isinstance(nsh, bool) or not isinstance(nsh, int) or \
+            not 0 <= nsh <= MAX_SHARED_EXPERTS:
+        raise ValueError(
+            f"num_shared_experts must be an integer in "
+            f"[0, {MAX_SHARED_EXPERTS}]; got {nsh!r}")
+    if cfg["expert_top_k"] + nsh > MAX_COMBINE_SLOTS:
+        raise ValueError(
+            f"expert_top_k + num_shared_experts must be <= "
+            f"{MAX_COMBINE_SLOTS}; got {cfg['expert_top_k']} + {nsh}")
+    if nsh > 0 and cfg["torch_dtype"] == 5:
+        raise ValueError(
+            f"num_shared_experts={nsh} is not supported with torch_dtype=5 "
+            "(MX fp8): shared experts occur in gated models, and gated + MX "
+            "is itself unsupported")
     if is_gated(cfg["hidden_act"]) and cfg["torch_dtype"] == 5:
         raise ValueError(
             f"hidden_act={cfg['hidden_act']} (gated) is not supported with "

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/flashmoe_abi.h"
 
@@ -864,6 +865,11 @@ struct GemmArgs {
                              // an expert's Wup (slot 0, at B) to its gating
                              // projection Wglu (slot 2); N is then the
                              // EFFECTIVE width 2P and the output pitch N/2
+  int nShared;               // PHASE 1, shared experts (num_shared_experts):
+  int nRoutedE;              // the combine slot pitch is topk + nShared, and
+                             // a z-slice e >= nRoutedE is a shared-expert
+                             // slice: scale 1, no gate_out read. Both are
+                             // wave-uniform; 0 / unused without shared experts
 };
 
 // Gated experts (hidden_act 2 SwiGLU, 3 GeGLU): h = act(g) * u with
@@ -1042,9 +1048,14 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
   const int cl = lane & 15;
   const int r0 = (lane >> 4) * 4;
   float* sScale = reinterpret_cast<float*>(Alds);  // reuse; loop is done
-  const bool multi = (PHASE == 1) && a.topk > 1;
+  // multi: write the per-(token, j) combine slot. A shared-expert slice
+  // (e >= nRoutedE) is unscaled and reads no gate_out column.
+  const bool multi = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
   if constexpr (PHASE == 1) {
-    if (multi) {
+    if (scaled) {
       __syncthreads();
       if (tid < BM) {
         const TPS tp = sTps[tid];
@@ -1079,7 +1090,7 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
       const int m = m0 + row;
       if ((uint32_t)m >= routed) continue;
       const TPS tp = sTps[row];
-      const float rowScale = multi ? sScale[row] : 1.0f;
+      const float rowScale = scaled ? sScale[row] : 1.0f;
       if constexpr (GATED) {
         // fragment pairs (2j, 2j+1) hold (g, u) of the same (row, p)
         const int P = N >> 1;
@@ -1110,7 +1121,7 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
             // non-atomic per-(token, j) combine slot (summed with the
             // kept mask in k_cast_combine; replaces fp32 atomics)
             reinterpret_cast<ET*>(a.O32)[
-                ((size_t)tpsTok(tp.tokenIdx) * a.topk + tpsJ(tp.tokenIdx)) *
+                ((size_t)tpsTok(tp.tokenIdx) * nSlot + tpsJ(tp.tokenIdx)) *
                     a.H + col] = ETr<ET>::fromf(v * rowScale);
           } else {
             reinterpret_cast<ET*>(
@@ -1395,8 +1406,13 @@ __device__ __forceinline__ bool gemm_job_body(
   // slot: write the per-(token, j) combine slot; scaled only at k>1
   // (the reference's k==1 CombineMode::single semantics are unscaled,
   // processor.cuh:173-204)
+  // A shared-expert slice (e >= nRoutedE, num_shared_experts > 0) is
+  // unscaled and reads no gate_out column; the slot pitch counts the
+  // shared slots. Both are block-uniform scalars.
   const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
-  const bool scaled = (PHASE == 1) && a.topk > 1;
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
   // PHASE 1 row scale (gate prob / probSum): fetched here, once per row,
   // so it is in LDS long before the epilogue and needs no barrier of its
   // own. Issued BEFORE the second prologue stage: the counted vmcnt
@@ -1628,7 +1644,7 @@ __device__ __forceinline__ bool gemm_job_body(
           if constexpr (PHASE == 1) {
             const TPS tp = sTps[row];  // {0, 1.0f} for rows past routed
             if (slot) {
-              orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * a.topk +
+              orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
                                 tpsJ(tp.tokenIdx)) * rowPitch;
               if (scaled) rowScale = sScale[row];
             } else {
@@ -1696,7 +1712,7 @@ __device__ __forceinline__ bool gemm_job_body(
         if (slot) {
           // non-atomic per-(token, j) combine slot (summed with the
           // kept mask in k_cast_combine; replaces fp32 atomics)
-          orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * a.topk +
+          orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
                             tpsJ(tp.tokenIdx)) * rowPitch;
           if (scaled) rowScale = sScale[row];
         } else {
@@ -2285,7 +2301,12 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
     __syncthreads();
   }
 
-  const bool multi = (PHASE == 1) && a.topk > 1;
+  // multi / scaled / nSlot: as in the 128^2 kernel (shared-expert slices
+  // write their slot unscaled)
+  const bool multi = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
   float bv[4] = {0.f, 0.f, 0.f, 0.f};
   if constexpr (HAS_BIAS) {
     // per-expert bias slabs when multi-expert (see the 128^2 kernel)
@@ -2303,7 +2324,7 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
     if ((uint32_t)m >= routed) continue;
     const TPS tp = sTps[tr + i];
     float rowScale = 1.0f;
-    if (multi)
+    if (scaled)
       rowScale = reinterpret_cast<const float*>(
                      a.gate_out)[(size_t)tpsTok(tp.tokenIdx) * a.PX +
                                  a.expertOffset + e] / tp.probSum;
@@ -2333,7 +2354,7 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
       } else if constexpr (PHASE == 1) {
         if (multi) {
           reinterpret_cast<float*>(a.O32)[
-              ((size_t)tpsTok(tp.tokenIdx) * a.topk + tpsJ(tp.tokenIdx)) *
+              ((size_t)tpsTok(tp.tokenIdx) * nSlot + tpsJ(tp.tokenIdx)) *
                   a.H + col] = v * rowScale;
         } else {
           reinterpret_cast<float*>(
@@ -2399,6 +2420,76 @@ __global__ void k_cast_combine(const T* __restrict__ cbuf,
           }
         }
       }
+      T ov[EPU];
+#pragma unroll
+      for (int q = 0; q < EPU; ++q) fromF(acc[q], ov[q]);
+      *reinterpret_cast<u32x4*>(out + (size_t)t * H + h) =
+          *reinterpret_cast<const u32x4*>(ov);
+    }
+  }
+  FM_AUX_STAMP(1, 1);
+}
+
+// 16 bytes of Element slots added into fp32 accumulators (the slot read
+// of the shared-expert combine below)
+template <typename T>
+__device__ __forceinline__ void accSlot16(const T* __restrict__ p,
+                                          float (&acc)[16 / sizeof(T)]) {
+  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const uint32_t vw = v[w];
+    if constexpr (__is_same(T, bf16)) {
+      const float2 f = __bfloat1622float2(
+          *reinterpret_cast<const __hip_bfloat162*>(&vw));
+      acc[2 * w] += f.x;
+      acc[2 * w + 1] += f.y;
+    } else if constexpr (__is_same(T, fp16)) {
+      const float2 f = __half22float2(*reinterpret_cast<const __half2*>(&vw));
+      acc[2 * w] += f.x;
+      acc[2 * w + 1] += f.y;
+    } else {
+      acc[w] += __uint_as_float(vw);
+    }
+  }
+}
+
+// Sibling of k_cast_combine for num_shared_experts > 0: the slots are
+// [S, K + nSh, H]; the K routed slots are kept-masked (kept is [S, K], the
+// gates write it at stride K), the nSh shared slots that follow are always
+// summed. fp32 sum in slot order, one rounding; same thread mapping as
+// k_cast_combine. A token with every routed slot dropped still gets its
+// shared terms, so K == 1 needs no zeroed moe_out either.
+template <typename T, int K>
+__global__ void k_cast_combine_shared(const T* __restrict__ cbuf,
+                                      const uint8_t* __restrict__ kept,
+                                      T* __restrict__ out, int S, int H,
+                                      int nSh) {
+  constexpr int EPU = 16 / sizeof(T);
+  FM_AUX_STAMP(1, 0);
+  const int cpt = max(1, H / EPU);
+  const int tpb = cpt < (int)blockDim.x ? (int)blockDim.x / cpt : 1;
+  const int tl = tpb > 1 ? (int)threadIdx.x / cpt : 0;
+  const int h0 = ((int)threadIdx.x - tl * cpt) * EPU;
+  const int hStep = tpb > 1 ? H : (int)blockDim.x * EPU;
+  const int nSlot = K + nSh;
+  for (int t = blockIdx.x * tpb + tl; t < S && tl < tpb;
+       t += gridDim.x * tpb) {
+    bool kp[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) kp[j] = kept[(size_t)t * K + j] != 0;
+    const T* slots = cbuf + (size_t)t * nSlot * H;
+    for (int h = h0; h < H; h += hStep) {
+      float acc[EPU];
+#pragma unroll
+      for (int q = 0; q < EPU; ++q) acc[q] = 0.0f;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        if (!kp[j]) continue;
+        accSlot16<T>(slots + (size_t)j * H + h, acc);
+      }
+      for (int s = 0; s < nSh; ++s)
+        accSlot16<T>(slots + (size_t)(K + s) * H + h, acc);
       T ov[EPU];
 #pragma unroll
       for (int q = 0; q < EPU; ++q) fromF(acc[q], ov[q]);
@@ -3127,9 +3218,15 @@ struct State {
   int wMats = 2;    // [P,H] slabs per expert: 2 (up, down), or 3 for gated
                     // experts (hidden_act 2/3: up, down, gating projection)
   bool gated = false;
+  // shared experts (num_shared_experts): nSh FFNs applied
+  // to every token, run as nV = nSh * ceil(S / min(EC, S)) extra z-slices
+  // of the two expert GEMM launches
+  int nSh = 0;
+  int nV = 0;
+  int32_t* sliceExpert = nullptr;  // [E + nV] z -> weight expert (nSh > 0)
   // workspace
-  TPS* tokenIds = nullptr;   // [E, pEC]
-  uint32_t* eC = nullptr;    // [E]
+  TPS* tokenIds = nullptr;   // [E + nV, pEC]; the nV tail is static
+  uint32_t* eC = nullptr;    // [E + nV]; the gates write the first E only
   float* logits32 = nullptr; // [S, E] gate logit accumulator
   float* gML = nullptr;      // [E] training aux: mean gate prob
   float* gMeC = nullptr;     // [E] training aux: routed fraction
@@ -3708,6 +3805,28 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   }
   g.gated = cfg->hidden_act >= 2;
   g.wMats = g.gated ? 3 : 2;
+  // shared experts: refused loudly where they cannot run (checked ahead of
+  // the gated + MX refusal so the message names the key that asked)
+  g.nSh = cfg->num_shared_experts;
+  if (g.nSh < 0 || g.nSh > 4) {
+    setErr("num_shared_experts must be in [0, 4]");
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (cfg->expert_top_k + g.nSh > 16) {
+    setErr("expert_top_k + num_shared_experts must be <= 16 (the combine "
+           "slot index j has four bits)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (g.nSh > 0 && cfg->dtype == 5) {
+    setErr("num_shared_experts > 0 is not supported with torch_dtype 5 (MX)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (g.nSh > 0 && world_size > 1) {
+    setErr("num_shared_experts > 0 is not supported with world_size > 1: "
+           "replicate the shared experts and run them on the local tokens "
+           "with fm_expert_ffn(local_e = nLx + s) (INTEGRATION.md)");
+    return FM_ERR_UNSUPPORTED;
+  }
   if (g.gated && cfg->dtype == 5) {
     // the MX up epilogue quantizes 64-column blocks in-register; halving
     // the output width there is separate work (open items)
@@ -3744,17 +3863,60 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   // (single-rank path: E experts; EP path: world*EC rows per local expert)
   g.nLxAlloc = (world_size == 1) ? g.E
                                  : g.nLx * DIVUP(world_size * g.EC, g.pEC);
-  FM_HIP_CHECK(hipMalloc(&g.tokenIds, (size_t)g.E * g.pEC * sizeof(TPS)));
+  // shared experts: each runs over ALL S tokens as ceil(S / C) virtual
+  // z-slices of C = min(EC, S) rows, so a slice has the geometry of a
+  // routed expert (rows <= EC <= pEC) and the launches need no new case
+  const int shC = std::min(g.EC, g.S);
+  const int shSlices = DIVUP(g.S, shC);
+  g.nV = g.nSh * shSlices;
+  g.nLxAlloc += g.nV;  // xM: one [pEC, P] slice per virtual slice (world 1)
+  const int nZ = g.E + g.nV;
+  FM_HIP_CHECK(hipMalloc(&g.tokenIds, (size_t)nZ * g.pEC * sizeof(TPS)));
   FM_HIP_CHECK(hipMalloc(&g.logits32, (size_t)g.S * g.E * sizeof(float)));
   FM_HIP_CHECK(hipMemset(g.logits32, 0, (size_t)g.S * g.E * sizeof(float)));
   FM_HIP_CHECK(hipMalloc(&g.gML, 2 * (size_t)g.E * sizeof(float)));
   g.gMeC = g.gML + g.E;
-  FM_HIP_CHECK(hipMalloc(&g.eC, (size_t)g.E * sizeof(uint32_t)));
+  FM_HIP_CHECK(hipMalloc(&g.eC, (size_t)nZ * sizeof(uint32_t)));
+  if (g.nV > 0) {
+    // The shared slices' routing is the identity and never changes, so
+    // the tail [E, E + nV) of tokenIds / eC is written ONCE, here. It
+    // survives every forward because both gates touch only the first E
+    // entries of eC (k_gate_fused copies E counts; the two-kernel gate
+    // zeroes E, in the logits kernel's block 0 or a memset of E words)
+    // and only the first E rows of tokenIds. Keep that true.
+    // Slice v = s * shSlices + c of shared expert s covers tokens
+    // [c * C, min(S, (c + 1) * C)) with j = k + s, probSum 1.
+    const int k = g.cfg.expert_top_k;
+    std::vector<TPS> hT((size_t)g.nV * g.pEC, TPS{0u, 1.0f});
+    std::vector<uint32_t> hC((size_t)g.nV);
+    std::vector<int32_t> hMap((size_t)nZ);
+    for (int e = 0; e < g.E; ++e) hMap[e] = e;
+    for (int s = 0; s < g.nSh; ++s)
+      for (int c = 0; c < shSlices; ++c) {
+        const int v = s * shSlices + c;
+        const int rows = std::min(shC, g.S - c * shC);
+        hC[v] = (uint32_t)rows;
+        hMap[g.E + v] = g.E + s;
+        for (int i = 0; i < rows; ++i)
+          hT[(size_t)v * g.pEC + i] =
+              TPS{(uint32_t)(c * shC + i) | ((uint32_t)(k + s) << 28), 1.0f};
+      }
+    FM_HIP_CHECK(hipMemcpy(g.tokenIds + (size_t)g.E * g.pEC, hT.data(),
+                           hT.size() * sizeof(TPS), hipMemcpyHostToDevice));
+    FM_HIP_CHECK(hipMemcpy(g.eC + g.E, hC.data(),
+                           hC.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice));
+    FM_HIP_CHECK(hipMalloc(&g.sliceExpert, (size_t)nZ * sizeof(int32_t)));
+    FM_HIP_CHECK(hipMemcpy(g.sliceExpert, hMap.data(),
+                           hMap.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice));
+  }
   FM_HIP_CHECK(hipMalloc(&g.xM, (size_t)g.nLxAlloc * g.pEC * g.P * g.esz));
   FM_HIP_CHECK(hipMalloc(&g.O32, (size_t)g.S * g.H * sizeof(float)));
   FM_HIP_CHECK(hipMemset(g.O32, 0, (size_t)g.S * g.H * sizeof(float)));
-  FM_HIP_CHECK(hipMalloc(&g.cbuf,
-                         (size_t)g.S * g.cfg.expert_top_k * g.H * g.esz));
+  // combine slots [S, k + nSh, H]; kept stays [S, k] (gate-written, stride k)
+  FM_HIP_CHECK(hipMalloc(&g.cbuf, (size_t)g.S * (g.cfg.expert_top_k + g.nSh) *
+                                      g.H * g.esz));
   FM_HIP_CHECK(hipMalloc(&g.kept, (size_t)g.S * g.cfg.expert_top_k));
   if (g.esz == 2 && g.E <= 64 && !g.cfg.is_training) {
     // k_gate_fused workspace; the ticket words are zeroed here once and
@@ -3820,6 +3982,7 @@ int fm_finalize(void) {
   (void)hipFree(g.tokenIds); (void)hipFree(g.eC); (void)hipFree(g.xM);
   (void)hipFree(g.O32);
   (void)hipFree(g.cbuf); (void)hipFree(g.kept);
+  if (g.sliceExpert) (void)hipFree(g.sliceExpert);
   (void)hipFree(g.logits32); (void)hipFree(g.gML);
   if (g.gateCtl) (void)hipFree(g.gateCtl);
   if (g.x8) { (void)hipFree(g.x8); (void)hipFree(g.xs);
@@ -3853,6 +4016,8 @@ int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,
 }
 
 int fm_get_num_local_experts(void) { return g.initialized ? g.nLx : -1; }
+
+int fm_get_num_shared_experts(void) { return g.initialized ? g.nSh : -1; }
 
 int fm_last_forward_fused(void) {
   return g.initialized ? (g.lastForwardFused ? 1 : 0) : -1;
@@ -4196,6 +4361,30 @@ static int launch_cast_combine(hipStream_t st, void* moe_out) {
   hipLaunchKernelGGL((k_cast_combine<T, KK>), dim3(blocks), dim3(256), 0, st, \
                      reinterpret_cast<const T*>(g.cbuf), g.kept,              \
                      reinterpret_cast<T*>(moe_out), g.S, g.H)
+#define CCS(T, KK)                                                            \
+  hipLaunchKernelGGL((k_cast_combine_shared<T, KK>), dim3(blocks), dim3(256), \
+                     0, st, reinterpret_cast<const T*>(g.cbuf), g.kept,       \
+                     reinterpret_cast<T*>(moe_out), g.S, g.H, g.nSh)
+  // shared experts: the [S, k + nSh, H] sibling (k == 1 included)
+#define CCS_K(T)                                                              \
+  switch (g.cfg.expert_top_k) {                                               \
+    case 1: CCS(T, 1); break;                                                 \
+    case 2: CCS(T, 2); break;                                                 \
+    case 3: CCS(T, 3); break;                                                 \
+    case 4: CCS(T, 4); break;                                                 \
+    case 5: CCS(T, 5); break;                                                 \
+    case 6: CCS(T, 6); break;                                                 \
+    case 7: CCS(T, 7); break;                                                 \
+    case 8: CCS(T, 8); break;                                                 \
+    default: setErr("bad topk"); return FM_ERR_UNSUPPORTED;                   \
+  }
+  if (g.nSh > 0) {
+    if (g.cfg.dtype == 3) { CCS_K(fp16) }
+    else if (g.esz == 2) { CCS_K(bf16) }
+    else { CCS_K(float) }
+    FM_HIP_CHECK(hipGetLastError());
+    return FM_OK;
+  }
 #define CC_K(T)                                                               \
   switch (g.cfg.expert_top_k) {                                               \
     case 2: CC(T, 2); break;                                                  \
@@ -4211,6 +4400,8 @@ static int launch_cast_combine(hipStream_t st, void* moe_out) {
   else if (g.esz == 2) { CC_K(bf16) }
   else { CC_K(float) }
 #undef CC_K
+#undef CCS_K
+#undef CCS
 #undef CC
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
@@ -4241,8 +4432,9 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   }
   // gated experts never take the fused kernel: its down-walk arrival
   // counts are keyed on the number of up N-tiles
+  // (nor do configs with shared experts: the fused walks know E experts)
   if (fusedEnabled() && g.esz == 2 && g.world == 1 && g.cfg.dtype != 5 &&
-      !g.gated) {
+      !g.gated && g.nSh == 0) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -4256,7 +4448,9 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // re-zeroes after reading)
   // k==1: zero moe_out so dropped tokens keep zeros (clearState,
   // moe.cuh:30-70); k>1 writes every element via k_cast_out instead
-  if (g.cfg.expert_top_k == 1) {
+  // (shared experts: k==1 goes through the combine slots too, and the
+  // combine writes every element - no memset)
+  if (g.cfg.expert_top_k == 1 && g.nSh == 0) {
     FM_HIP_CHECK(hipMemsetAsync(moe_out, 0, (size_t)g.S * g.H * g.esz, st));
   }
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[1], st));
@@ -4287,13 +4481,22 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   up.EC = g.EC; up.pEC = g.pEC; up.PX = g.PX;
   up.topk = g.cfg.expert_top_k; up.act = g.cfg.hidden_act;
   up.expertOffset = 0; up.nRows = 0; up.H = g.H;
+  // shared experts ride both launches as nV extra z-slices (static routing
+  // tail, fm_initialize); null map / zero counts when there are none
+  const int nZ = g.E + g.nV;
+  if (g.nSh > 0) {
+    up.segExpert = g.sliceExpert;
+    up.nShared = g.nSh;
+    up.nRoutedE = g.E;
+    up.slotAlways = 1;
+  }
   const bool mxEpiQuant =
       (g.cfg.dtype == 5) && mxWideN(g.pEC, g.P, g.E);
   if (mxEpiQuant) {
     up.out8 = g.xM8;       // 256-tile up epilogue quantizes in-register
     up.outScales = g.xMs;  // (skips the separate k_quant_mx xM pass)
   }
-  rc = launch_group_gemm(st, 0, up, g.pEC, g.E);
+  rc = launch_group_gemm(st, 0, up, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[3], st));
 
@@ -4316,11 +4519,11 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   dn.moe_out = moe_out;
   dn.strideAExpert = (long long)g.pEC * g.P;
   dn.K = g.P; dn.N = g.H;
-  rc = launch_group_gemm(st, 1, dn, g.pEC, g.E);
+  rc = launch_group_gemm(st, 1, dn, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[4], st));
 
-  if (g.cfg.expert_top_k > 1) {
+  if (g.cfg.expert_top_k > 1 || g.nSh > 0) {
     int rc2 = launch_cast_combine(st, moe_out);
     if (rc2 != FM_OK) return rc2;
   }

@@ -9,7 +9,7 @@ import ctypes
 import os
 
 from . import _ext
-from .config import (element_size_of, expert_mats, load_config,
+from .config import (element_size_of, expert_mats, load_config, num_shared,
                      torch_dtype_of, weight_dtype_of)
 
 _state = {
@@ -62,6 +62,7 @@ def initialize(config_path: str | None = None, rank: int | None = None,
         mini_batch=cfg["mini_batch"],
         dtype=cfg["torch_dtype"],
         is_training=cfg["is_training"],
+        num_shared_experts=num_shared(cfg),
     )
     _ext.check(lib.fm_initialize(ctypes.byref(c), rank, world_size), "fm_initialize")
     _state.update(initialized=True, cfg=cfg, rank=rank, world=world_size)
@@ -111,10 +112,19 @@ def get_compiled_config() -> dict:
 
 
 def get_num_local_experts() -> int:
-    """Mirror of _C.get_num_local_experts (python_bindings.cu:185-189)."""
+    """Mirror of _C.get_num_local_experts (python_bindings.cu:185-189):
+    the ROUTED local experts; shared experts are not counted."""
     if not _state["initialized"]:
         raise RuntimeError("Must call initialize() first")
     return _ext.load().fm_get_num_local_experts()
+
+
+def get_num_shared_experts() -> int:
+    """num_shared_experts of the initialized config: the expert-weights
+    tensor carries this many slabs after the routed ones."""
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    return _ext.load().fm_get_num_shared_experts()
 
 
 def _validate_forward_args(input, gate_weights, expert_weights):
@@ -147,7 +157,13 @@ def _validate_forward_args(input, gate_weights, expert_weights):
             f"Gate weights must be [H={H}, E={E}]. Got "
             f"[{gate_weights.size(0)}, {gate_weights.size(1)}]"
         )
-    if expert_weights.size(0) != nLx:
+    nSh = get_num_shared_experts()
+    if expert_weights.size(0) != nLx + nSh:
+        if nSh:
+            raise ValueError(
+                f"Expert count mismatch. Expected {nLx} local + {nSh} shared "
+                f"experts ([{nLx + nSh}, ...], num_shared_experts={nSh}), "
+                f"got {expert_weights.size(0)}")
         raise ValueError(
             f"Expert count mismatch. Expected {nLx} local experts, got {expert_weights.size(0)}"
         )
@@ -178,7 +194,10 @@ def _validate_forward_args(input, gate_weights, expert_weights):
 def moe_forward(input, gate_weights, expert_weights):
     """Mirror of _C.moe_forward (python_bindings.cu:17-151): one DMoE
     forward on this rank's tokens. Single-rank path; world>1 uses the EP
-    pipeline in ep.py (same result per rank)."""
+    pipeline in ep.py (same result per rank). With
+    num_shared_experts = nSh > 0 expert_weights is [nLx + nSh, mats, P, H]
+    (shared slabs last) and every token also receives the unscaled sum of
+    the shared FFNs."""
     import torch
 
     S, H, E, P, nLx = _validate_forward_args(input, gate_weights, expert_weights)

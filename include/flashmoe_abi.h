@@ -51,7 +51,30 @@ extern "C" {
  * expert stride is 3*P*H. Unsupported with a gated hidden_act
  * (FM_ERR_UNSUPPORTED): b_up != NULL (every entry point), and dtype 5
  * (at fm_initialize). Gated forwards always run the multi-kernel path,
- * never the single-launch fused kernel. */
+ * never the single-launch fused kernel.
+ *
+ * num_shared_experts (nSh, 0..4, expert_top_k + nSh <= 16): SHARED experts,
+ * FFNs applied to every token, unrouted and unscaled, and added to the
+ * routed result (DeepSeek-MoE / Qwen-MoE):
+ *   moe_out[t] = Element( sum_{j<k, kept} Element(scale_j * FFN_{e_j}(x_t))
+ *                       + sum_{s<nSh} Element(FFN_{nLx+s}(x_t)) )
+ * summed in fp32 in that order, rounded once. The routed terms are exactly
+ * those of nSh == 0; a token whose routed slots were all dropped still
+ * receives its shared terms. Shared experts use the config's hidden_act, P
+ * and dtype; their weight slabs TRAIL the routed ones in the same slot
+ * layout, so expert_w is [nLx + nSh, mats, P, H] and b_up / b_dn, where
+ * given, are [nLx + nSh, P] / [nLx + nSh, H] (indexed by weight-expert
+ * id). A shared expert of width n*P is exactly the sum of n shared experts
+ * of width P (column split of Wup/Wglu, row split of Wdn). They run as extra
+ * z-slices of the two grouped expert GEMM launches of fm_moe_forward /
+ * fm_moe_forward_phased (always the multi-kernel path). The staged entry
+ * points (fm_gate_forward, fm_expert_ffn*, fm_combine*) ignore them;
+ * fm_expert_ffn can address a shared slab with local_e = nLx + s.
+ * FM_ERR_UNSUPPORTED at fm_initialize: nSh outside 0..4, expert_top_k +
+ * nSh > 16, nSh > 0 with dtype 5, nSh > 0 with world_size > 1.
+ *
+ * ABI NOTE: the struct GREW by this trailing field. A caller built against
+ * the eleven-field layout must be rebuilt (or zero the new field). */
 typedef struct fm_config {
   int32_t num_experts;
   int32_t expert_top_k;
@@ -66,6 +89,7 @@ typedef struct fm_config {
   int32_t mini_batch;
   int32_t dtype;
   int32_t is_training;
+  int32_t num_shared_experts; /* 0 = none (see above); last field */
 } fm_config;
 
 /* Replaces flashmoe::initialize (python_bindings.cu:157-159,
@@ -85,8 +109,12 @@ int fm_finalize(void);
 int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,
                            int64_t* PX, int64_t* element_size);
 
-/* Replaces _C.get_num_local_experts (python_bindings.cu:185-189). */
+/* Replaces _C.get_num_local_experts (python_bindings.cu:185-189). The
+ * ROUTED local experts only: shared experts are not counted. */
 int fm_get_num_local_experts(void);
+
+/* num_shared_experts of the frozen config (-1 before fm_initialize). */
+int fm_get_num_shared_experts(void);
 
 /* 1 if the last fm_moe_forward / fm_moe_forward_phased ran the
  * single-launch fused kernel, 0 if it ran the multi-kernel path, -1
@@ -102,7 +130,9 @@ int fm_last_forward_fused(void);
  * gate_w:    flat E*H Element buffer (the torch [H,E] tensor's storage,
  *            used as a row-major [E,H] matrix - reference quirk,
  *            moe.cuh:107-109; see oracle/moe_oracle.py docstring)
- * expert_w:  [nLx, 2, P, H] Element ([e][0]=Wup [P,H]; [e][1] flat,
+ * expert_w:  (nLx + num_shared_experts leading entries when the config
+ *            has shared experts)
+ *            [nLx, 2, P, H] Element ([e][0]=Wup [P,H]; [e][1] flat,
  *            used as [H,P] - moe.cuh:114-116); [nLx, 3, P, H] with
  *            [e][2]=Wglu [P,H] when hidden_act is gated (2/3)
  * b_up/b_dn: [nLx, P] / [nLx, H] Element or NULL (reference zero-fills,

@@ -1,8 +1,12 @@
 """Randomized parity sweep: many random (shape, E, k, act, dtype) configs
 vs the CPU oracle on one GPU. Exact-output comparisons use single-tile
 or overflow-free capacities (routing set determinism); run via
-  python tools/parity_sweep.py [n_cases] [seed]
-Exits nonzero on the first failure.
+  python tools/parity_sweep.py [n_cases] [seed] [p_shared]
+Exits nonzero on the first failure. p_shared (default 0) is the
+probability that a case also draws num_shared_experts in 1..4 (never with
+dtype 5, which refuses them); those cases compare against
+tests/shared_ref.py. The draw uses its own generator, so the (shape, E, k,
+act, dtype) sequence of a seed does not depend on p_shared.
 """
 import json
 import os
@@ -17,9 +21,13 @@ import torch
 from oracle.moe_oracle import OracleConfig, moe_forward as oracle_forward
 from flashmoe_amd import moe
 from flashmoe_amd.config import torch_dtype_of, weight_dtype_of
+from tests.shared_ref import shared_moe_forward
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1234)
+seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1234
+rng = random.Random(seed)
+p_shared = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
+rng_sh = random.Random(seed + 7919)  # own stream: rng's draws are untouched
 
 def EC_of(cfg):
     S = cfg["sequence_len"] * cfg["mini_batch"]
@@ -52,17 +60,22 @@ for case in range(n_cases):
            "mini_batch": 1, "moe_frequency": 1, "num_experts": E,
            "num_layers": 1, "sequence_len": S, "torch_dtype": dtype,
            "vocab_size": 32000}
+    nsh = 0
+    if dtype != 5 and rng_sh.random() < p_shared:
+        nsh = rng_sh.choice([1, 1, 2, 3, 4])
+        cfg["num_shared_experts"] = nsh
     f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
     json.dump(cfg, f)
     f.close()
-    desc = f"S={S} H={H} P={P} E={E} k={k} act={act} dt={dtype} cf={cf} drop={drop}"
+    desc = f"S={S} H={H} P={P} E={E} k={k} act={act} dt={dtype} cf={cf} drop={drop}" + (
+        f" nSh={nsh}" if nsh else "")
     try:
         moe.initialize(f.name, rank=0, world_size=1)
         dt = torch_dtype_of(dtype)
         gten = torch.Generator().manual_seed(1000 + case)
         x = torch.randn(1, S, H, generator=gten).to(dt).cuda()
         gw = torch.randn(H, E, generator=gten).to(dt).cuda()
-        ew = torch.randn(E, 2, P, H, generator=gten).to(
+        ew = torch.randn(E + nsh, 2, P, H, generator=gten).to(
             weight_dtype_of(dtype)).cuda()
         out = moe.moe_forward(x, gw, ew)
         torch.cuda.synchronize()
@@ -70,9 +83,14 @@ for case in range(n_cases):
         ocfg = OracleConfig(num_experts=E, expert_top_k=k, capacity_factor=cf,
                             drop_tokens=drop, hidden_act=act, element=element,
                             mx_fp8=(dtype == 5))
-        ref = oracle_forward(x.view(S, H).float().cpu().numpy(),
-                             gw.float().cpu().numpy().reshape(-1),
-                             ew.float().cpu().numpy(), ocfg)
+        if nsh:
+            ref = shared_moe_forward(x.view(S, H).float().cpu().numpy(),
+                                     gw.float().cpu().numpy().reshape(-1),
+                                     ew.float().cpu().numpy(), ocfg, nsh)
+        else:
+            ref = oracle_forward(x.view(S, H).float().cpu().numpy(),
+                                 gw.float().cpu().numpy().reshape(-1),
+                                 ew.float().cpu().numpy(), ocfg)
         got = out.view(S, H).float().cpu().numpy()
         want = ref["moe_out"]
         # multi-tile + any expert over capacity: the kept-token SET is

@@ -1,9 +1,16 @@
 """Single-GPU shape benchmark for any BASELINE-like MoE shape.
 
-Usage: python tools/shape_bench.py [--hidden-act A] [S H P E topk [steps [dtype]]]
+Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
+                                   [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
 times a gated (SwiGLU/GeGLU) expert with [E, 3, P, H] weights.
+--shared N times a config with num_shared_experts = N ([E + N, ...]
+weights, the shared experts folded into the two expert GEMM launches).
+--compose N times the hand composition of the same result on a config
+WITHOUT the key: moe_forward on the routed slabs, fm_expert_ffn over all S
+rows per shared slab, and a torch add (us_per_fwd only covers the whole
+composition; the phase times are those of the routed forward alone).
 """
 import ctypes
 import json
@@ -24,6 +31,15 @@ if "--hidden-act" in argv:
     i = argv.index("--hidden-act")
     hidden_act = int(argv[i + 1])
     del argv[i:i + 2]
+n_shared = n_compose = 0
+for flag in ("--shared", "--compose"):
+    if flag in argv:
+        i = argv.index(flag)
+        if flag == "--shared":
+            n_shared = int(argv[i + 1])
+        else:
+            n_compose = int(argv[i + 1])
+        del argv[i:i + 2]
 args = [int(a) for a in argv]
 S, H, P, E, topk = (args + [4096, 2048, 8192, 64, 2][len(args):])[:5]
 steps = args[5] if len(args) > 5 else 30
@@ -34,6 +50,8 @@ cfg = {"capacity_factor": 1, "drop_tokens": 1, "expert_top_k": topk,
        "hidden_size": H, "intermediate_size": P, "mini_batch": 1,
        "moe_frequency": 1, "num_experts": E, "num_layers": 1,
        "sequence_len": S, "torch_dtype": dtype_code, "vocab_size": 32000}
+if n_shared:
+    cfg["num_shared_experts"] = n_shared
 f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
 json.dump(cfg, f)
 f.close()
@@ -44,18 +62,35 @@ adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
 x = torch.randn(1, S, H, dtype=adt, device="cuda")
 gw = torch.randn(H, E, dtype=adt, device="cuda")
-ew = torch.randn(E, expert_mats(hidden_act), P, H, dtype=torch.float32,
-                 device="cuda").to(wdt)
+ew_all = torch.randn(E + n_shared + n_compose, expert_mats(hidden_act), P, H,
+                     dtype=torch.float32, device="cuda").to(wdt)
+ew = ew_all[:E + n_shared]  # what moe_forward sees (a leading slice)
+lib = _ext.load()
+sh_out = torch.empty(S, H, dtype=adt, device="cuda")
+
+
+def forward():
+    out = moe.moe_forward(x, gw, ew)
+    if n_compose:
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        for s_ in range(n_compose):
+            _ext.check(lib.fm_expert_ffn(
+                st, ctypes.c_void_p(x.data_ptr()),
+                ctypes.c_void_p(ew_all.data_ptr()), None, None,
+                ctypes.c_void_p(sh_out.data_ptr()), S, E + s_), "fm_expert_ffn")
+            out = out + sh_out.view_as(out)
+    return out
+
+
 for _ in range(max(3, steps // 3)):
-    moe.moe_forward(x, gw, ew)
+    forward()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(steps):
-    moe.moe_forward(x, gw, ew)
+    forward()
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
 
-lib = _ext.load()
 ms = (ctypes.c_float * 4)()
 acc = [0.0] * 4
 out = torch.empty_like(x)
@@ -73,7 +108,9 @@ flops = 4.0 * S * topk * H * P  # upper bound (pre-capacity-drop)
 gemm_ms = acc[1] + acc[2]
 print(json.dumps({
     "workload": (f"1xMI355X S={S} H={H} P={P} E={E} top-{topk} "
-                 f"dtype{dtype_code} act{hidden_act} CF=1 drop"),
+                 f"dtype{dtype_code} act{hidden_act} CF=1 drop"
+                 + (f" shared={n_shared}" if n_shared else "")
+                 + (f" compose={n_compose}" if n_compose else "")),
     "us_per_fwd": round(dt * 1e6, 1),
     "tokens_per_s": round(S / dt),
     "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
