@@ -5,9 +5,11 @@ from flashmoe_amd import (  # noqa: F401
     finalize,
     get_compiled_config,
     get_num_local_experts,
+    get_router,
     initialize,
     moe_forward,
     run_moe,
+    set_score_bias,
 )
 from flashmoe_amd import moe as _C  # noqa: F401  (the _C-equivalent surface)
 

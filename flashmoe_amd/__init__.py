@@ -9,8 +9,10 @@ from .moe import (  # noqa: F401
     get_compiled_config,
     get_num_local_experts,
     get_num_shared_experts,
+    get_router,
     initialize,
     moe_forward,
+    set_score_bias,
 )
 from .ops import run_moe  # noqa: F401
 
@@ -23,4 +25,6 @@ __all__ = [
     "moe_forward",
     "get_num_local_experts",
     "get_num_shared_experts",
+    "set_score_bias",
+    "get_router",
 ]

@@ -34,9 +34,33 @@ class FMConfig(ctypes.Structure):
     ]
 
 
+class FMRouterConfig(ctypes.Structure):
+    # mirrors fm_router_config in include/flashmoe_abi.h; the keyword-less
+    # constructor yields zeros, NOT the defaults - use router_defaults()
+    _fields_ = [
+        ("scoring_func", ctypes.c_int32),
+        ("norm_topk_prob", ctypes.c_int32),
+        ("n_group", ctypes.c_int32),
+        ("topk_group", ctypes.c_int32),
+        ("group_score", ctypes.c_int32),
+        ("routed_scaling_factor", ctypes.c_float),
+        ("score_bias", ctypes.c_void_p),
+    ]
+
+
+def router_defaults() -> FMRouterConfig:
+    return FMRouterConfig(scoring_func=0, norm_topk_prob=1, n_group=1,
+                          topk_group=1, group_score=0,
+                          routed_scaling_factor=1.0, score_bias=None)
+
+
 def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     p = ctypes.c_void_p
     i64 = ctypes.c_int64
+    lib.fm_set_router.argtypes = [ctypes.POINTER(FMRouterConfig)]
+    lib.fm_set_router.restype = ctypes.c_int
+    lib.fm_get_router.argtypes = [ctypes.POINTER(FMRouterConfig)]
+    lib.fm_get_router.restype = ctypes.c_int
     lib.fm_initialize.argtypes = [ctypes.POINTER(FMConfig), ctypes.c_int, ctypes.c_int]
     lib.fm_initialize.restype = ctypes.c_int
     lib.fm_finalize.argtypes = []

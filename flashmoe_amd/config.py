@@ -71,6 +71,86 @@ def num_shared(cfg: dict) -> int:
     return int(cfg.get("num_shared_experts", 0))
 
 
+# Router keys (all optional; absent = the reference's router: softmax over
+# all experts, plain top-k, weights p_j / sum_selected p). See
+# fm_router_config in include/flashmoe_abi.h and DESIGN.md par.5j.
+ROUTER_DEFAULTS = {
+    "scoring_func": 0,           # 0 softmax, 1 sigmoid
+    "norm_topk_prob": 1,         # 0: weights are the raw scores
+    "n_group": 1,                # group-limited top-k (1 = no limit)
+    "topk_group": 1,
+    "group_score": 0,            # 0 max, 1 sum of the two largest
+    "routed_scaling_factor": 1.0,
+}
+MAX_ROUTER_GROUPS = 16
+MAX_VARIANT_EXPERTS = 256  # sigmoid / bias / groups: the route kernel's LDS
+
+
+def router_of(cfg: dict) -> dict:
+    """The router keys of a config with the defaults filled in."""
+    return {k: cfg.get(k, d) for k, d in ROUTER_DEFAULTS.items()}
+
+
+def router_is_default(cfg: dict) -> bool:
+    return router_of(cfg) == ROUTER_DEFAULTS
+
+
+def _validate_router(cfg: dict) -> None:
+    """The fm_set_router refusals that the config alone decides (a score
+    bias is attached later, moe.set_score_bias)."""
+    import math
+
+    r = router_of(cfg)
+    E, k = cfg["num_experts"], cfg["expert_top_k"]
+    for key in ("scoring_func", "norm_topk_prob", "group_score"):
+        v = r[key]
+        if isinstance(v, bool) or not isinstance(v, int) or v not in (0, 1):
+            raise ValueError(f"{key} must be 0 or 1; got {v!r}")
+    for key in ("n_group", "topk_group"):
+        v = r[key]
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{key} must be an integer; got {v!r}")
+    G, TG = r["n_group"], r["topk_group"]
+    if not 1 <= G <= MAX_ROUTER_GROUPS:
+        raise ValueError(f"n_group must be in [1, {MAX_ROUTER_GROUPS}]; got {G}")
+    if E % G:
+        raise ValueError(f"num_experts={E} is not divisible by n_group={G}")
+    if not 1 <= TG <= G:
+        raise ValueError(f"topk_group must be in [1, n_group={G}]; got {TG}")
+    if k > TG * (E // G):
+        raise ValueError(
+            f"expert_top_k={k} exceeds the topk_group * num_experts / n_group "
+            f"= {TG * (E // G)} experts of the kept groups")
+    if r["group_score"] == 1 and E // G < 2:
+        raise ValueError(
+            f"group_score=1 (sum of top 2) needs at least 2 experts per "
+            f"group; n_group={G} leaves {E // G}")
+    f = r["routed_scaling_factor"]
+    if isinstance(f, bool) or not isinstance(f, (int, float)) or \
+            not math.isfinite(f) or f <= 0:
+        raise ValueError(
+            f"routed_scaling_factor must be a finite number > 0; got {f!r}")
+    if k == 1 and r["norm_topk_prob"] == 0:
+        raise ValueError(
+            "norm_topk_prob=0 is not supported with expert_top_k=1: the "
+            "top-1 direct store is unscaled")
+    if k == 1 and float(f) != 1.0:
+        raise ValueError(
+            "routed_scaling_factor != 1 is not supported with expert_top_k=1: "
+            "the top-1 direct store is unscaled")
+    if cfg["is_training"] and not router_is_default(cfg):
+        key = next(k_ for k_, d in ROUTER_DEFAULTS.items() if r[k_] != d)
+        raise ValueError(
+            f"a non-default {key} is not supported with is_training=1: the "
+            "aux-loss accumulators are softmax-specific")
+    if E > MAX_VARIANT_EXPERTS and (r["scoring_func"] == 1 or G > 1):
+        key = "scoring_func=1" if r["scoring_func"] == 1 else f"n_group={G}"
+        raise ValueError(
+            f"{key} is not supported with num_experts > {MAX_VARIANT_EXPERTS} "
+            "(the route kernel's LDS budget); norm_topk_prob and "
+            "routed_scaling_factor work at every num_experts")
+
+
 def load_config(path: str | None = None) -> dict:
     path = path or DEFAULT_CONFIG_PATH
     with open(path) as f:
@@ -106,4 +186,5 @@ def load_config(path: str | None = None) -> dict:
             f"hidden_act={cfg['hidden_act']} (gated) is not supported with "
             "torch_dtype=5 (MX fp8): the MX up epilogue cannot yet halve its "
             "output width")
+    _validate_router(cfg)
     return cfg

@@ -261,13 +261,101 @@ __global__ __launch_bounds__(256) void k_gate_logits(
 // Reads the tile's logits from logits32 and RE-ZEROES them (keeps the
 // split-K logits accumulate memset-free).
 // ---------------------------------------------------------------------------
-template <typename T, int K>
+// ---------------------------------------------------------------------------
+// Router variants (fm_router_config): sigmoid scoring, a
+// selection bias, group-limited top-k, unnormalised / scaled weights. Both
+// gates compile them behind the template switch RV; the RV = false
+// instantiations are the legacy code, untouched. In an RV instantiation
+// the token's LDS logits row is rewritten IN PLACE with the scores s (no
+// second tile: 128 x (E + 1) x 4 B is 131 KB at E = 256), the selection
+// score c[e] = row[e] + sB[e] is formed in the scan from an LDS copy of the
+// bias (zeros without one), and the group limit enters as the initial
+// taken-mask, so the scan itself has no new branch. selLogits (softmax, no
+// bias, group_score 0): c is monotone in the logits, so the row keeps the
+// logits and selection, mCw and gate_out are computed exactly as the legacy
+// code computes them - a pure norm / factor variant selects bit-identically
+// to the default router.
+// ---------------------------------------------------------------------------
+struct RouterP {
+  const float* bias;  // device fp32 [E] or null
+  float factor;       // routed_scaling_factor
+  int scoring, norm, G, TG, gscore;
+  int selLogits;      // scoring 0 && !bias && gscore 0
+};
+
+constexpr int kMaxGroups = 16;
+
+// scores of one thread's chunk [e0, e1) of a token row; SUBS threads per
+// token. Softmax: m / inv_d by the legacy reduction order. Returns with the
+// row holding s (or still the logits when selLogits).
+__device__ __forceinline__ void rv_scores(float* lrow, int e0, int e1,
+                                          int SUBS, const RouterP& rp,
+                                          float& m, float& inv_d) {
+  m = 0.0f;
+  inv_d = 1.0f;
+  if (rp.scoring == 0) {
+    m = -INFINITY;
+    for (int e = e0; e < e1; ++e) m = fmaxf(m, lrow[e]);
+    for (int off = 1; off < SUBS; off <<= 1)
+      m = fmaxf(m, __shfl_xor(m, off, SUBS));
+    float d = 0.0f;
+    for (int e = e0; e < e1; ++e) d += __expf(lrow[e] - m);
+    for (int off = 1; off < SUBS; off <<= 1) d += __shfl_xor(d, off, SUBS);
+    inv_d = 1.0f / d;
+    if (!rp.selLogits)
+      for (int e = e0; e < e1; ++e) lrow[e] = __expf(lrow[e] - m) * inv_d;
+  } else {
+    for (int e = e0; e < e1; ++e) lrow[e] = 1.0f / (1.0f + __expf(-lrow[e]));
+  }
+}
+
+// group scores of the groups sub, sub + SUBS, ... of one token: max c, or
+// the sum of the two largest c (other threads' chunks: after a barrier)
+__device__ __forceinline__ void rv_group_scores(const float* lrow,
+                                                const float* sB, float* sGrow,
+                                                int sub, int SUBS, int E,
+                                                const RouterP& rp) {
+  const int gs = E / rp.G;
+  for (int gi = sub; gi < rp.G; gi += SUBS) {
+    float a = -INFINITY, b = -INFINITY;  // largest, second largest
+    for (int e = gi * gs; e < (gi + 1) * gs; ++e) {
+      const float c = lrow[e] + sB[e];
+      if (c > a) { b = a; a = c; }
+      else if (c > b) b = c;
+    }
+    sGrow[gi] = rp.gscore ? a + b : a;
+  }
+}
+
+// initial taken-mask of the chunk [e0, e1): the experts outside the TG best
+// groups (strict-> first-index argmax, TG times). Every thread of the token
+// computes the same kept set from the same LDS group scores.
+__device__ __forceinline__ unsigned long long rv_group_taken(
+    const float* sGrow, int e0, int e1, int E, const RouterP& rp) {
+  uint32_t keepG = 0u;
+  for (int i = 0; i < rp.TG; ++i) {
+    float bv = -INFINITY;
+    int bi = -1;
+    for (int gi = 0; gi < rp.G; ++gi) {
+      const float v = sGrow[gi];
+      if (!((keepG >> gi) & 1u) && v > bv) { bv = v; bi = gi; }
+    }
+    if (bi >= 0) keepG |= 1u << bi;
+  }
+  const int gs = E / rp.G;
+  unsigned long long taken = 0ull;
+  for (int e = e0; e < e1; ++e)
+    if (!((keepG >> (e / gs)) & 1u)) taken |= 1ull << (e - e0);
+  return taken;
+}
+
+template <typename T, int K, bool RV = false>
 __device__ __forceinline__ void route_tile_core(
     char* smem, float* __restrict__ logits32, T* __restrict__ gate_out,
     TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC,
     uint8_t* __restrict__ kept, float* __restrict__ gML,
     float* __restrict__ gMeC, int S, int E, int PX, int EC, int pEC,
-    int m0) {
+    int m0, const RouterP& rp = RouterP{}) {
   // TT tokens per pass: 128 normally; 64 half-passes at E > 256 so the
   // fp32 logits tile fits LDS (64 x 513 x 4 B = 131 KB at E = 512).
   // SUBS = 512/TT threads cooperate per token (chunk <= 64 experts each,
@@ -285,6 +373,8 @@ __device__ __forceinline__ void route_tile_core(
   float* sInv = reinterpret_cast<float*>(base + E);                // [TT] 1/d
   float* sMax = sInv + TT;                                         // [TT]
   float* sCw = sMax + TT;                                          // [TT] mCw
+  float* sB = sCw + TT;             // RV only: [E] selection bias
+  float* sGrp = sB + E;             // RV only: [TT][kMaxGroups] group scores
   const int tid = threadIdx.x;
   for (int pass = 0; pass < 128 / TT; ++pass) {
   const int pm0 = m0 + pass * TT;
@@ -295,9 +385,56 @@ __device__ __forceinline__ void route_tile_core(
     logits[row * (E + 1) + col] = *src;
     *src = 0.0f;
   }
+  if constexpr (RV)
+    for (int e = tid; e < E; e += 512) sB[e] = rp.bias ? rp.bias[e] : 0.0f;
   __syncthreads();
 
-  {
+  if constexpr (RV) {
+    // 512 = TT * SUBS threads: every thread owns a (token, chunk), so the
+    // barriers below are reached by all of them
+    const int token = tid / SUBS;
+    const int sub = tid % SUBS;
+    float* lrow = logits + token * (E + 1);
+    const int chunk = (E + SUBS - 1) / SUBS;  // <= 64: u64 taken-mask
+    const int e0 = min(E, sub * chunk);
+    const int e1 = min(E, e0 + chunk);
+    float m, inv_d;
+    rv_scores(lrow, e0, e1, SUBS, rp, m, inv_d);
+    if (sub == 0) {
+      sInv[token] = inv_d;  // read by the gate_out pass when selLogits
+      sMax[token] = m;
+    }
+    __syncthreads();  // rows hold s: group scores read other chunks
+    if (rp.G > 1)
+      rv_group_scores(lrow, sB, sGrp + token * kMaxGroups, sub, SUBS, E, rp);
+    __syncthreads();
+    unsigned long long takenM =
+        rp.G > 1 ? rv_group_taken(sGrp + token * kMaxGroups, e0, e1, E, rp)
+                 : 0ull;
+    float mCw = 0.0f;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      float lv = -INFINITY;
+      int li = E;  // sentinel sorts after every real index
+      for (int e = e0; e < e1; ++e) {
+        const bool tk = (takenM >> (e - e0)) & 1ull;
+        const float c = lrow[e] + sB[e];
+        if (!tk && c > lv) { lv = c; li = e; }
+      }
+      for (int off = 1; off < SUBS; off <<= 1) {
+        const float ov = __shfl_xor(lv, off, SUBS);
+        const int oi = __shfl_xor(li, off, SUBS);
+        if (ov > lv || (ov == lv && oi < li)) { lv = ov; li = oi; }
+      }
+      if (li >= e0 && li < e1) takenM |= 1ull << (li - e0);
+      if (sub == 0) {
+        sel[token * K + i] = (uint16_t)li;
+        if (rp.selLogits) mCw += __expf(lv - m) * inv_d;
+        else if (li < E) mCw += lrow[li];
+      }
+    }
+    if (sub == 0) sCw[token] = (rp.norm ? mCw : 1.0f) / rp.factor;
+  } else {
     const int token = tid / SUBS;
     const int sub = tid % SUBS;
     if (token < TT) {
@@ -358,7 +495,13 @@ __device__ __forceinline__ void route_tile_core(
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int col = col0 + q;
-      const float pv = (col < E) ? __expf(lrow[col] - mR) * ivR : 0.0f;
+      float pv;
+      if constexpr (RV)  // the row already holds s unless selLogits
+        pv = (col < E) ? (rp.selLogits ? __expf(lrow[col] - mR) * ivR
+                                       : lrow[col])
+                       : 0.0f;
+      else
+        pv = (col < E) ? __expf(lrow[col] - mR) * ivR : 0.0f;
       fromF(pv, v.x[q]);
     }
     *reinterpret_cast<V8*>(gate_out + (size_t)(pm0 + row) * PX + col0) = v;
@@ -395,6 +538,14 @@ __device__ __forceinline__ void route_tile_core(
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       const int e = sel[tid * K + i];
+      if constexpr (RV) {
+        // e == E: no selectable expert was left (a bias of -inf or NaN
+        // scores); the slot is dropped, never indexed
+        if (e >= E) {
+          if (kept) kept[(size_t)(pm0 + tid) * K + i] = 0;
+          continue;
+        }
+      }
       const uint32_t slot = base[e] + localIdx[tid * K + i];
       const bool keep = slot < (uint32_t)EC;
       if (keep) {
@@ -407,17 +558,18 @@ __device__ __forceinline__ void route_tile_core(
   }  // pass loop
 }
 
-template <typename T, int K>
+template <typename T, int K, bool RV = false>
 __global__ __launch_bounds__(512) void k_gate_route(
     float* __restrict__ logits32, T* __restrict__ gate_out,
     TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC, int S, int E,
     int PX, int EC, int pEC, float* __restrict__ gML,
-    float* __restrict__ gMeC, uint8_t* __restrict__ kept) {
+    float* __restrict__ gMeC, uint8_t* __restrict__ kept, RouterP rp) {
   // gML/gMeC: training-mode aux-loss accumulators (gate.cuh:273-299,
   // 763-773; types.cuh:936-958). Null in inference mode.
+  // rp: read by the RV instantiations only
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  route_tile_core<T, K>(smem, logits32, gate_out, tokenIds, eC, kept, gML,
-                        gMeC, S, E, PX, EC, pEC, blockIdx.x * 128);
+  route_tile_core<T, K, RV>(smem, logits32, gate_out, tokenIds, eC, kept, gML,
+                            gMeC, S, E, PX, EC, pEC, blockIdx.x * 128, rp);
 }
 
 // ---------------------------------------------------------------------------
@@ -522,13 +674,14 @@ __device__ unsigned long long g_auxStamps[FM_AUX_KERNELS][FM_AUX_BLOCKS][2];
 #define FM_AUX_STAMP(k, i) do {} while (0)
 #endif
 
-template <typename T, int K, int TB>
+template <typename T, int K, int TB, bool RV = false>
 __global__ __launch_bounds__(TB * 16) void k_gate_fused(
     const T* __restrict__ x, const T* __restrict__ gate_w,
     T* __restrict__ gate_out, uint16_t* gateSel, float* gateCw,
     uint32_t* tilesDone, uint32_t* tileArrive, uint32_t* eCacc,
     TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC,
-    uint8_t* __restrict__ kept, int H, int E, int PX, int EC, int pEC) {
+    uint8_t* __restrict__ kept, int H, int E, int PX, int EC, int pEC,
+    RouterP rp /* read by the RV instantiations only */) {
   constexpr int NT = TB * 16;    // threads
   constexpr int NWV = NT / 64;   // waves: TB/16 row groups x 4 K ranges
   constexpr int SUB = 128 / TB;  // sub-blocks per tile
@@ -585,7 +738,70 @@ __global__ __launch_bounds__(TB * 16) void k_gate_fused(
   __syncthreads();
 
   // ---- softmax / top-k: four threads per token (route_tile_core) -----
-  if (tid < TB * 4) {
+  if constexpr (RV) {
+    // router variant: scores in place, group scores through LDS, group
+    // limit as the initial taken-mask (see RouterP). The two barriers are
+    // outside the tid test; mCw in the hand-off payload carries D.
+    constexpr int SUBS = 4;
+    __shared__ float sB[64];
+    __shared__ float sGrp[TB * kMaxGroups];
+    const bool act = tid < TB * 4;
+    const int token = act ? tid / SUBS : 0;
+    const int sub = tid % SUBS;
+    float* lrow = logits + token * LDL;
+    const int chunk = (E + SUBS - 1) / SUBS;
+    const int e0 = min(E, sub * chunk);
+    const int e1 = min(E, e0 + chunk);
+    float m = 0.0f, inv_d = 1.0f;
+    if (tid >= NT - 64 && lane < E)  // the last wave: idle until the barrier
+      sB[lane] = rp.bias ? rp.bias[lane] : 0.0f;
+    if (act) {
+      rv_scores(lrow, e0, e1, SUBS, rp, m, inv_d);
+      if (sub == 0) {
+        sInv[token] = inv_d;
+        sMax[token] = m;
+      }
+    }
+    __syncthreads();
+    if (act && rp.G > 1)
+      rv_group_scores(lrow, sB, sGrp + token * kMaxGroups, sub, SUBS, E, rp);
+    __syncthreads();
+    if (act) {
+      uint32_t takenM =  // chunk <= 16
+          rp.G > 1 ? (uint32_t)rv_group_taken(sGrp + token * kMaxGroups, e0,
+                                              e1, E, rp)
+                   : 0u;
+      float mCw = 0.0f;
+#pragma unroll
+      for (int i = 0; i < K; ++i) {
+        float lv = -INFINITY;
+        int li = E;  // sentinel sorts after every real index
+        for (int e = e0; e < e1; ++e) {
+          const bool tk = (takenM >> (e - e0)) & 1u;
+          const float c = lrow[e] + sB[e];
+          if (!tk && c > lv) { lv = c; li = e; }
+        }
+#pragma unroll
+        for (int off = 1; off < SUBS; off <<= 1) {
+          const float ov = __shfl_xor(lv, off, SUBS);
+          const int oi = __shfl_xor(li, off, SUBS);
+          if (ov > lv || (ov == lv && oi < li)) { lv = ov; li = oi; }
+        }
+        if (li >= e0 && li < e1) takenM |= 1u << (li - e0);
+        if (sub == 0) {
+          __hip_atomic_store(gateSel + (size_t)(m0 + token) * K + i,
+                             (uint16_t)li, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+          if (rp.selLogits) mCw += __expf(lv - m) * inv_d;
+          else if (li < E) mCw += lrow[li];
+        }
+      }
+      if (sub == 0)
+        __hip_atomic_store(gateCw + m0 + token,
+                           (rp.norm ? mCw : 1.0f) / rp.factor,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else if (tid < TB * 4) {
     constexpr int SUBS = 4;
     const int token = tid / SUBS;
     const int sub = tid % SUBS;
@@ -649,7 +865,13 @@ __global__ __launch_bounds__(TB * 16) void k_gate_fused(
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
       const int col = col0 + q;
-      const float pv = (col < E) ? __expf(lrow[col] - mR) * ivR : 0.0f;
+      float pv;
+      if constexpr (RV)  // the row already holds s unless selLogits
+        pv = (col < E) ? (rp.selLogits ? __expf(lrow[col] - mR) * ivR
+                                       : lrow[col])
+                       : 0.0f;
+      else
+        pv = (col < E) ? __expf(lrow[col] - mR) * ivR : 0.0f;
       fromF(pv, v.x[q]);
     }
     *reinterpret_cast<V8*>(gate_out + (size_t)(m0 + row) * PX + col0) = v;
@@ -3271,8 +3493,26 @@ struct State {
   int nCU = 0;
   int wallClockKHz = 100000;      // s_memrealtime rate (ticks per ms)
   bool lastForwardFused = false;
+  // router variant (fm_set_router); reset with the State
+  fm_router_config router{0, 1, 1, 1, 0, 1.0f, nullptr};
+  bool routerRV = false;    // any non-default field: the RV gate kernels
+  uint32_t routerGen = 0;   // bumped per fm_set_router: part of the graph key
 };
 State g;
+
+// kernel-side view of g.router
+static RouterP routerParams() {
+  RouterP rp{};
+  rp.bias = g.router.score_bias;
+  rp.factor = g.router.routed_scaling_factor;
+  rp.scoring = g.router.scoring_func;
+  rp.norm = g.router.norm_topk_prob;
+  rp.G = g.router.n_group;
+  rp.TG = g.router.topk_group;
+  rp.gscore = g.router.group_score;
+  rp.selLogits = (rp.scoring == 0 && !rp.bias && rp.gscore == 0) ? 1 : 0;
+  return rp;
+}
 
 thread_local char g_err[512] = "";
 
@@ -3333,8 +3573,9 @@ template <typename T>
 int launch_gate_fused(hipStream_t st, const void* x, const void* gate_w,
                       void* gate_out, int64_t S) {
   char* ws = reinterpret_cast<char*>(g.gateCtl);
-#define GATE_FUSED(KK)                                                        \
-  hipLaunchKernelGGL((k_gate_fused<T, KK, kGateTB>),                          \
+  const RouterP rp = routerParams();
+#define GATE_FUSED_RV(KK, RVV)                                                \
+  hipLaunchKernelGGL((k_gate_fused<T, KK, kGateTB, RVV>),                     \
                      dim3((unsigned)(S / kGateTB)), dim3(kGateTB * 16), 0,    \
                      st, reinterpret_cast<const T*>(x),                       \
                      reinterpret_cast<const T*>(gate_w),                      \
@@ -3343,7 +3584,13 @@ int launch_gate_fused(hipStream_t st, const void* x, const void* gate_w,
                      reinterpret_cast<float*>(ws + g.gateCwOff), g.gateCtl,   \
                      reinterpret_cast<uint32_t*>(ws + g.gateArriveOff),       \
                      reinterpret_cast<uint32_t*>(ws + g.gateEcOff),           \
-                     g.tokenIds, g.eC, g.kept, g.H, g.E, g.PX, g.EC, g.pEC)
+                     g.tokenIds, g.eC, g.kept, g.H, g.E, g.PX, g.EC, g.pEC,   \
+                     rp)
+#define GATE_FUSED(KK)                                                        \
+  do {                                                                        \
+    if (g.routerRV) { GATE_FUSED_RV(KK, true); }                              \
+    else { GATE_FUSED_RV(KK, false); }                                        \
+  } while (0)
   switch (g.cfg.expert_top_k) {
     case 1: GATE_FUSED(1); break;
     case 2: GATE_FUSED(2); break;
@@ -3356,6 +3603,7 @@ int launch_gate_fused(hipStream_t st, const void* x, const void* gate_w,
     default: setErr("unsupported expert_top_k (1..8)"); return FM_ERR_UNSUPPORTED;
   }
 #undef GATE_FUSED
+#undef GATE_FUSED_RV
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
 }
@@ -3379,9 +3627,14 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
   const size_t ldsL = gate_lds_bytes(Ec, g.esz);
   // route arena: TT = 64-token half-passes at E > 256 (route_tile_core)
   const int rTT = (g.E > 256) ? 64 : 128;
+  // (RV: + the LDS bias copy and the per-token group scores)
   const size_t ldsR = (size_t)rTT * (g.E + 1) * sizeof(float) +
                       rTT * 8 * 2 * sizeof(uint16_t) + g.E * sizeof(uint32_t) +
-                      3 * rTT * sizeof(float) + 64;
+                      3 * rTT * sizeof(float) + 64 +
+                      (g.routerRV ? (size_t)(g.E + rTT * kMaxGroups) *
+                                        sizeof(float)
+                                  : 0);
+  const RouterP rp = routerParams();
   float* gMLp = g.cfg.is_training ? g.gML : nullptr;
   float* gMeCp = g.cfg.is_training ? g.gMeC : nullptr;
   if (g.cfg.is_training)
@@ -3397,16 +3650,21 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
                        reinterpret_cast<const T*>(gate_w), g.logits32, g.eC,  \
                        (int)S, g.H, g.E, Hc);                                 \
   } while (0)
-#define GATE_ROUTE(T, KK)                                                     \
+#define GATE_ROUTE_RV(T, KK, RVV)                                             \
   do {                                                                        \
     if (ldsR > 64 * 1024)                                                     \
       (void)hipFuncSetAttribute(                                                    \
-          reinterpret_cast<const void*>(&k_gate_route<T, KK>),                \
+          reinterpret_cast<const void*>(&k_gate_route<T, KK, RVV>),           \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsR);             \
-    hipLaunchKernelGGL((k_gate_route<T, KK>), dim3(tiles), dim3(512), ldsR,   \
-                       st, g.logits32, reinterpret_cast<T*>(gate_out),        \
+    hipLaunchKernelGGL((k_gate_route<T, KK, RVV>), dim3(tiles), dim3(512),    \
+                       ldsR, st, g.logits32, reinterpret_cast<T*>(gate_out),  \
                        g.tokenIds, g.eC, (int)S, g.E, g.PX, g.EC, g.pEC,      \
-                       gMLp, gMeCp, g.kept);                                  \
+                       gMLp, gMeCp, g.kept, rp);                              \
+  } while (0)
+#define GATE_ROUTE(T, KK)                                                     \
+  do {                                                                        \
+    if (g.routerRV) { GATE_ROUTE_RV(T, KK, true); }                           \
+    else { GATE_ROUTE_RV(T, KK, false); }                                     \
   } while (0)
 #define GATE_K(T)                                                             \
   switch (g.cfg.expert_top_k) {                                               \
@@ -3448,6 +3706,7 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
   }
 #undef GATE_K
 #undef GATE_ROUTE
+#undef GATE_ROUTE_RV
 #undef GATE_LOGITS
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
@@ -3773,6 +4032,8 @@ int fm_built_for_gfx950(void) { return 1; }
 int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   if (g.initialized) { setErr("already initialized"); return FM_ERR_STATE; }
   if (!cfg) { setErr("null config"); return FM_ERR_STATE; }
+  g.router = State{}.router;  // a fresh config starts from the default router
+  g.routerRV = false;
   g.cfg = *cfg;
   g.rank = rank;
   g.world = world_size;
@@ -4021,6 +4282,89 @@ int fm_get_num_shared_experts(void) { return g.initialized ? g.nSh : -1; }
 
 int fm_last_forward_fused(void) {
   return g.initialized ? (g.lastForwardFused ? 1 : 0) : -1;
+}
+
+int fm_set_router(const fm_router_config* r) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  const fm_router_config def = State{}.router;
+  const fm_router_config c = r ? *r : def;
+  const int E = g.E, k = g.cfg.expert_top_k;
+#define FM_ROUTER_REFUSE(...)                                                 \
+  do {                                                                        \
+    snprintf(g_err, sizeof(g_err), __VA_ARGS__);                              \
+    return FM_ERR_UNSUPPORTED;                                                \
+  } while (0)
+  if (c.scoring_func != 0 && c.scoring_func != 1)
+    FM_ROUTER_REFUSE("scoring_func must be 0 (softmax) or 1 (sigmoid); got %d",
+                     c.scoring_func);
+  if (c.norm_topk_prob != 0 && c.norm_topk_prob != 1)
+    FM_ROUTER_REFUSE("norm_topk_prob must be 0 or 1; got %d", c.norm_topk_prob);
+  if (c.group_score != 0 && c.group_score != 1)
+    FM_ROUTER_REFUSE("group_score must be 0 (max) or 1 (sum of top 2); got %d",
+                     c.group_score);
+  if (c.n_group < 1 || c.n_group > kMaxGroups)
+    FM_ROUTER_REFUSE("n_group must be in [1, %d]; got %d", kMaxGroups,
+                     c.n_group);
+  if (E % c.n_group)
+    FM_ROUTER_REFUSE("num_experts = %d is not divisible by n_group = %d", E,
+                     c.n_group);
+  if (c.topk_group < 1 || c.topk_group > c.n_group)
+    FM_ROUTER_REFUSE("topk_group must be in [1, n_group = %d]; got %d",
+                     c.n_group, c.topk_group);
+  if (k > c.topk_group * (E / c.n_group))
+    FM_ROUTER_REFUSE("expert_top_k = %d exceeds the topk_group * E / n_group = "
+                     "%d experts of the kept groups", k,
+                     c.topk_group * (E / c.n_group));
+  if (c.group_score == 1 && E / c.n_group < 2)
+    FM_ROUTER_REFUSE("group_score 1 (sum of top 2) needs at least 2 experts "
+                     "per group; n_group = %d leaves %d", c.n_group,
+                     E / c.n_group);
+  if (!std::isfinite(c.routed_scaling_factor) ||
+      !(c.routed_scaling_factor > 0.0f))
+    FM_ROUTER_REFUSE("routed_scaling_factor must be finite and > 0; got %g",
+                     (double)c.routed_scaling_factor);
+  if (k == 1 && c.norm_topk_prob == 0)
+    FM_ROUTER_REFUSE("norm_topk_prob 0 is not supported with expert_top_k 1: "
+                     "the top-1 direct store is unscaled");
+  if (k == 1 && c.routed_scaling_factor != 1.0f)
+    FM_ROUTER_REFUSE("routed_scaling_factor != 1 is not supported with "
+                     "expert_top_k 1: the top-1 direct store is unscaled");
+  const bool rv = c.scoring_func != def.scoring_func ||
+                  c.norm_topk_prob != def.norm_topk_prob ||
+                  c.n_group != def.n_group || c.topk_group != def.topk_group ||
+                  c.group_score != def.group_score ||
+                  c.routed_scaling_factor != def.routed_scaling_factor ||
+                  c.score_bias != nullptr;
+  if (rv && g.cfg.is_training) {
+    const char* key = c.scoring_func != 0 ? "scoring_func"
+                      : c.norm_topk_prob != 1 ? "norm_topk_prob"
+                      : c.n_group != 1 ? "n_group"
+                      : c.topk_group != 1 ? "topk_group"
+                      : c.group_score != 0 ? "group_score"
+                      : c.routed_scaling_factor != 1.0f ? "routed_scaling_factor"
+                                                        : "score_bias";
+    FM_ROUTER_REFUSE("a non-default %s is not supported with is_training 1: "
+                     "the aux-loss accumulators are softmax-specific", key);
+  }
+  if (E > 256 && (c.scoring_func == 1 || c.score_bias || c.n_group > 1)) {
+    const char* key = c.scoring_func == 1 ? "scoring_func 1"
+                      : c.score_bias ? "score_bias" : "n_group > 1";
+    FM_ROUTER_REFUSE("%s is not supported with num_experts > 256 (the route "
+                     "kernel's LDS budget); norm_topk_prob and "
+                     "routed_scaling_factor work at every E", key);
+  }
+#undef FM_ROUTER_REFUSE
+  g.router = c;
+  g.routerRV = rv;
+  ++g.routerGen;  // never replay a forward captured under another router
+  return FM_OK;
+}
+
+int fm_get_router(fm_router_config* out) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (!out) { setErr("null router config"); return FM_ERR_STATE; }
+  *out = g.router;
+  return FM_OK;
 }
 
 static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
@@ -4433,8 +4777,10 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // gated experts never take the fused kernel: its down-walk arrival
   // counts are keyed on the number of up N-tiles
   // (nor do configs with shared experts: the fused walks know E experts)
+  // (nor does a non-default router: k_moe_fused routes with the legacy
+  // route_tile_core)
   if (fusedEnabled() && g.esz == 2 && g.world == 1 && g.cfg.dtype != 5 &&
-      !g.gated && g.nSh == 0) {
+      !g.gated && g.nSh == 0 && !g.routerRV) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -4552,7 +4898,8 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                   const_cast<void*>(expert_w), const_cast<void*>(b_up),
                   const_cast<void*>(b_dn), gate_out, moe_out,
                   reinterpret_cast<void*>(static_cast<uintptr_t>(
-                      (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
+                      (uint64_t)g.routerGen << 40 | (uint64_t)S << 2 |
+                      (gateFusedEnabled() ? 2 : 0) |
                       (fusedEnabled() ? 1 : 0)))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;

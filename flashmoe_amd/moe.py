@@ -9,7 +9,8 @@ import ctypes
 import os
 
 from . import _ext
-from .config import (element_size_of, expert_mats, load_config, num_shared,
+from .config import (MAX_VARIANT_EXPERTS, element_size_of, expert_mats,
+                     load_config, num_shared, router_is_default, router_of,
                      torch_dtype_of, weight_dtype_of)
 
 _state = {
@@ -19,6 +20,7 @@ _state = {
     "world": 1,
     "gate_out": None,  # persistent [S, PX] buffer (internal, like the
     # reference's flat-buffer gate output, python_bindings.cu:70-74)
+    "score_bias": None,  # the fp32 [E] tensor fm_set_router borrows
 }
 
 
@@ -65,7 +67,15 @@ def initialize(config_path: str | None = None, rank: int | None = None,
         num_shared_experts=num_shared(cfg),
     )
     _ext.check(lib.fm_initialize(ctypes.byref(c), rank, world_size), "fm_initialize")
-    _state.update(initialized=True, cfg=cfg, rank=rank, world=world_size)
+    _state.update(initialized=True, cfg=cfg, rank=rank, world=world_size,
+                  score_bias=None)
+    if not router_is_default(cfg):
+        try:
+            _apply_router()
+        except Exception:
+            lib.fm_finalize()
+            _state.update(initialized=False, cfg=None)
+            raise
     # persistent gate_out buffer
     S = cfg["sequence_len"] * cfg["mini_batch"]
     PX = (cfg["num_experts"] + 63) // 64 * 64
@@ -79,12 +89,73 @@ def finalize():
     if not _state["initialized"]:
         raise RuntimeError("finalize() before initialize()")
     _ext.check(_ext.load().fm_finalize(), "fm_finalize")
-    _state.update(initialized=False, cfg=None, gate_out=None)
+    _state.update(initialized=False, cfg=None, gate_out=None, score_bias=None)
     _state.pop("p2p", None)        # heap freed by fm_finalize
     _state.pop("ep_buffers", None)
     # a P2P setup failure is scoped to one initialize/finalize cycle
     _state.pop("p2p_failed", None)
     _state.pop("p2p_validated", None)
+
+
+def _apply_router():
+    """fm_set_router from the config's router keys and the current bias."""
+    r = router_of(_state["cfg"])
+    bias = _state["score_bias"]
+    c = _ext.FMRouterConfig(
+        scoring_func=r["scoring_func"], norm_topk_prob=r["norm_topk_prob"],
+        n_group=r["n_group"], topk_group=r["topk_group"],
+        group_score=r["group_score"],
+        routed_scaling_factor=float(r["routed_scaling_factor"]),
+        score_bias=bias.data_ptr() if bias is not None else None)
+    _ext.check(_ext.load().fm_set_router(ctypes.byref(c)), "fm_set_router")
+
+
+def set_score_bias(bias):
+    """Attach (or, with None, detach) the selection bias of the router:
+    a contiguous fp32 [E] CUDA tensor added to the scores for SELECTION
+    only, never to the weights (DeepSeek-V3's e_score_correction_bias).
+    The tensor is borrowed by the library and kept alive here; its contents
+    may be rewritten in place between forwards."""
+    import torch
+
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    if bias is not None:
+        E = _state["cfg"]["num_experts"]
+        if not isinstance(bias, torch.Tensor) or not bias.is_cuda:
+            raise ValueError("score bias must be a CUDA tensor")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (E,) or \
+                not bias.is_contiguous():
+            raise ValueError(
+                f"score bias must be a contiguous float32 [E={E}] tensor; got "
+                f"{bias.dtype} {tuple(bias.shape)}")
+        if E > MAX_VARIANT_EXPERTS:
+            raise ValueError(
+                f"a score bias is not supported with num_experts > "
+                f"{MAX_VARIANT_EXPERTS} (the route kernel's LDS budget)")
+    prev = _state["score_bias"]
+    _state["score_bias"] = bias
+    try:
+        _apply_router()
+    except Exception:
+        _state["score_bias"] = prev
+        raise
+
+
+def get_router() -> dict:
+    """The active router (fm_get_router): the config keys plus
+    "score_bias", the attached tensor or None."""
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    c = _ext.FMRouterConfig()
+    _ext.check(_ext.load().fm_get_router(ctypes.byref(c)), "fm_get_router")
+    bias = _state["score_bias"]
+    assert (c.score_bias or 0) == (bias.data_ptr() if bias is not None else 0)
+    return {"scoring_func": c.scoring_func, "norm_topk_prob": c.norm_topk_prob,
+            "n_group": c.n_group, "topk_group": c.topk_group,
+            "group_score": c.group_score,
+            "routed_scaling_factor": float(c.routed_scaling_factor),
+            "score_bias": bias}
 
 
 def get_compiled_config() -> dict:
@@ -227,7 +298,7 @@ def moe_forward(input, gate_weights, expert_weights):
 
 
 def gate_output():
-    """The [S, PX] softmax probabilities of the last forward (the
-    reference exposes these as the first slab of its output buffer,
-    moe.cuh:128-131)."""
+    """The [S, PX] scores of the last forward: softmax probabilities, or
+    sigmoid scores under scoring_func 1 (the reference exposes these as the
+    first slab of its output buffer, moe.cuh:128-131)."""
     return _state["gate_out"]

@@ -104,6 +104,52 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size);
  * bootstrap.cuh:561-588): frees the workspace. */
 int fm_finalize(void);
 
+/* Router variant. fm_config describes the reference's
+ * router: softmax over the E experts, plain top-k, combine weights
+ * p_j / sum_selected p. This struct selects the routers of Qwen-MoE and
+ * DeepSeek-V2/V3; every field defaults to the reference's behaviour. For
+ * a token with fp32 logits l[e]:
+ *   s[e] = softmax(l)[e] (scoring_func 0) | 1 / (1 + exp(-l[e])) (1)
+ *   c[e] = s[e] + score_bias[e]           selection score; the bias never
+ *                                         enters the weights
+ *   groups: the E experts form n_group contiguous groups of E / n_group;
+ *           a group's score is max c (group_score 0) or the sum of its two
+ *           largest c (group_score 1); the topk_group best groups are kept
+ *           (iterative strict-> first-index argmax) and only their experts
+ *           can be selected. n_group 1 = no limit.
+ *   top-k:  iterative strict-> first-index argmax over c, k times
+ *   D     = (norm_topk_prob ? sum_j s[e_j] : 1.0f) / routed_scaling_factor
+ * gate_out[t, :E] = Element(s), every tokenIds entry of the token carries
+ * probSum = D, and the combine weight of selection j is Element(s[e_j]) / D.
+ * Capacity, ordering and the shared-expert tail are those of the default.
+ *
+ * fm_set_router is valid after fm_initialize; fm_initialize and
+ * fm_finalize reset the router to the defaults; NULL sets the defaults.
+ * score_bias is BORROWED: the caller keeps it alive until the next
+ * fm_set_router / fm_finalize and may rewrite its contents in place
+ * between forwards. A set call invalidates the captured forward graph. A
+ * non-default router always runs the multi-kernel path.
+ * FM_ERR_UNSUPPORTED (the message names the key): num_experts not
+ * divisible by n_group; n_group outside 1..16; topk_group outside
+ * 1..n_group; expert_top_k > topk_group * E / n_group; group_score 1 with
+ * fewer than 2 experts per group; routed_scaling_factor not finite or <= 0;
+ * expert_top_k == 1 with norm_topk_prob 0 or a factor != 1 (the top-1
+ * direct store is unscaled); is_training with any non-default field (the
+ * aux-loss accumulators are softmax-specific); E > 256 with scoring_func 1,
+ * a bias or n_group > 1 (norm_topk_prob and routed_scaling_factor alone
+ * work at every E). */
+typedef struct fm_router_config {
+  int32_t scoring_func;          /* 0 softmax (default), 1 sigmoid */
+  int32_t norm_topk_prob;        /* 1 (default) | 0 */
+  int32_t n_group;               /* default 1 */
+  int32_t topk_group;            /* default 1 */
+  int32_t group_score;           /* 0 max (default), 1 sum of top 2 */
+  float   routed_scaling_factor; /* default 1.0f */
+  const float* score_bias;       /* device fp32 [E] or NULL; borrowed */
+} fm_router_config;
+int fm_set_router(const fm_router_config* r); /* NULL = defaults */
+int fm_get_router(fm_router_config* out);
+
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */
 int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,
@@ -158,7 +204,10 @@ int fm_gate_forward(void* stream, const void* x, const void* gate_w,
 
 /* Copy routing results out: routed[e] = min(eC[e], EC) and the ordered
  * token slots (token index + probSum) per expert, for the host to build
- * the all-to-all. Device-to-host; synchronizes `stream`. */
+ * the all-to-all. prob_sum is the token's combine denominator D of the
+ * active router (fm_router_config: the sum of the selected scores by
+ * default, 1 / routed_scaling_factor when norm_topk_prob is 0).
+ * Device-to-host; synchronizes `stream`. */
 int fm_read_routing(void* stream, uint32_t* routed_counts /* [E] */,
                     uint32_t* token_idx /* [E*EC] */,
                     float* prob_sum /* [E*EC] */);

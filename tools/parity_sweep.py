@@ -1,12 +1,18 @@
 """Randomized parity sweep: many random (shape, E, k, act, dtype) configs
 vs the CPU oracle on one GPU. Exact-output comparisons use single-tile
 or overflow-free capacities (routing set determinism); run via
-  python tools/parity_sweep.py [n_cases] [seed] [p_shared]
+  python tools/parity_sweep.py [n_cases] [seed] [p_shared] [p_router]
 Exits nonzero on the first failure. p_shared (default 0) is the
 probability that a case also draws num_shared_experts in 1..4 (never with
 dtype 5, which refuses them); those cases compare against
 tests/shared_ref.py. The draw uses its own generator, so the (shape, E, k,
-act, dtype) sequence of a seed does not depend on p_shared.
+act, dtype) sequence of a seed does not depend on p_shared. p_router
+(default 0) is the probability that an inference case with k > 1 also draws
+a router variant (sigmoid scoring, a selection bias, a group limit,
+unnormalised / scaled weights; groups, sigmoid and bias only at E <= 256),
+again from its own generator; those cases scale the gate weights by
+1/sqrt(H) (sigmoid scores off saturation), compare against
+tests/router_ref.py and mask near-tie rows by its two margins.
 """
 import json
 import os
@@ -21,6 +27,7 @@ import torch
 from oracle.moe_oracle import OracleConfig, moe_forward as oracle_forward
 from flashmoe_amd import moe
 from flashmoe_amd.config import torch_dtype_of, weight_dtype_of
+from tests.router_ref import router_moe_forward
 from tests.shared_ref import shared_moe_forward
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -28,6 +35,25 @@ seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1234
 rng = random.Random(seed)
 p_shared = float(sys.argv[3]) if len(sys.argv) > 3 else 0.0
 rng_sh = random.Random(seed + 7919)  # own stream: rng's draws are untouched
+p_router = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0
+rng_rt = random.Random(seed + 104729)  # own stream, likewise
+
+
+def draw_router(E, k):
+    """A router variant that fm_set_router accepts for (E, k > 1)."""
+    r = {"norm_topk_prob": rng_rt.choice([0, 1]),
+         "routed_scaling_factor": rng_rt.choice([1.0, 2.5, 16.0])}
+    use_bias = False
+    if E <= 256:
+        r["scoring_func"] = rng_rt.choice([0, 1])
+        use_bias = rng_rt.random() < 0.5
+        groups = [(G, TG, gsc) for G in (2, 4, 8, 16) if E % G == 0
+                  for TG in range(1, G + 1) for gsc in (0, 1)
+                  if k <= TG * (E // G) and (gsc == 0 or E // G >= 2)]
+        if groups and rng_rt.random() < 0.7:
+            r["n_group"], r["topk_group"], r["group_score"] = \
+                rng_rt.choice(groups)
+    return r, use_bias
 
 def EC_of(cfg):
     S = cfg["sequence_len"] * cfg["mini_batch"]
@@ -64,26 +90,44 @@ for case in range(n_cases):
     if dtype != 5 and rng_sh.random() < p_shared:
         nsh = rng_sh.choice([1, 1, 2, 3, 4])
         cfg["num_shared_experts"] = nsh
+    router, use_bias = None, False
+    if k > 1 and not cfg["is_training"] and rng_rt.random() < p_router:
+        router, use_bias = draw_router(E, k)
+        cfg.update(router)
     f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
     json.dump(cfg, f)
     f.close()
     desc = f"S={S} H={H} P={P} E={E} k={k} act={act} dt={dtype} cf={cf} drop={drop}" + (
-        f" nSh={nsh}" if nsh else "")
+        f" nSh={nsh}" if nsh else "") + (
+        f" router={router} bias={int(use_bias)}" if router else "")
     try:
         moe.initialize(f.name, rank=0, world_size=1)
         dt = torch_dtype_of(dtype)
         gten = torch.Generator().manual_seed(1000 + case)
         x = torch.randn(1, S, H, generator=gten).to(dt).cuda()
-        gw = torch.randn(H, E, generator=gten).to(dt).cuda()
+        gw = torch.randn(H, E, generator=gten)
+        if router:
+            gw = gw / H ** 0.5
+        gw = gw.to(dt).cuda()
         ew = torch.randn(E + nsh, 2, P, H, generator=gten).to(
             weight_dtype_of(dtype)).cuda()
+        bias = None
+        if use_bias:
+            bias = (0.1 * torch.randn(E, generator=gten)).cuda()
+            moe.set_score_bias(bias)
         out = moe.moe_forward(x, gw, ew)
         torch.cuda.synchronize()
         element = {0: "fp32", 2: "bf16", 3: "fp16", 4: "bf16", 5: "bf16"}[dtype]
         ocfg = OracleConfig(num_experts=E, expert_top_k=k, capacity_factor=cf,
                             drop_tokens=drop, hidden_act=act, element=element,
                             mx_fp8=(dtype == 5))
-        if nsh:
+        if router:
+            ref = router_moe_forward(
+                x.view(S, H).float().cpu().numpy(),
+                gw.float().cpu().numpy().reshape(-1),
+                ew.float().cpu().numpy(), ocfg, router,
+                bias.cpu().numpy() if use_bias else None, n_shared=nsh)
+        elif nsh:
             ref = shared_moe_forward(x.view(S, H).float().cpu().numpy(),
                                      gw.float().cpu().numpy().reshape(-1),
                                      ew.float().cpu().numpy(), ocfg, nsh)
@@ -134,6 +178,8 @@ for case in range(n_cases):
             # whose tie_margin is below threshold; anything else is a bug.
             # bf16/fp16 logits carry ~1e-3-scale summation-order noise
             near = ref["tie_margin"] < (1e-3 if element == "fp32" else 5e-3)
+            if router:  # margins in units of the selection score
+                near = (ref["margin_sel"] < 1e-4) | (ref["margin_grp"] < 1e-4)
             bad_rows = ~okm.all(axis=1)
             if not (bad_rows & ~near).any():
                 okm_final = True

@@ -1,6 +1,7 @@
 """Single-GPU shape benchmark for any BASELINE-like MoE shape.
 
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
+                                   [--router qwen|v2|v3|sigmoid]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -11,6 +12,11 @@ weights, the shared experts folded into the two expert GEMM launches).
 WITHOUT the key: moe_forward on the routed slabs, fm_expert_ffn over all S
 rows per shared slab, and a torch add (us_per_fwd only covers the whole
 composition; the phase times are those of the routed forward alone).
+--router times a router variant: qwen = softmax without
+renormalisation; v2 = DeepSeek-V2 (groups 8/3 by max, no renormalisation,
+factor 16); v3 = DeepSeek-V3 (sigmoid + bias, groups 8/4 by top-2 sum,
+renormalised, factor 2.5); sigmoid = sigmoid + bias, renormalised, no groups.
+Its gate weights are scaled by 1/sqrt(H), the bias is 0.1 * randn(E).
 """
 import ctypes
 import json
@@ -40,6 +46,19 @@ for flag in ("--shared", "--compose"):
         else:
             n_compose = int(argv[i + 1])
         del argv[i:i + 2]
+ROUTERS = {
+    "qwen": dict(norm_topk_prob=0),
+    "v2": dict(n_group=8, topk_group=3, group_score=0, norm_topk_prob=0,
+               routed_scaling_factor=16.0),
+    "v3": dict(scoring_func=1, n_group=8, topk_group=4, group_score=1,
+               norm_topk_prob=1, routed_scaling_factor=2.5),
+    "sigmoid": dict(scoring_func=1, norm_topk_prob=1),
+}
+router = None
+if "--router" in argv:
+    i = argv.index("--router")
+    router = argv[i + 1]
+    del argv[i:i + 2]
 args = [int(a) for a in argv]
 S, H, P, E, topk = (args + [4096, 2048, 8192, 64, 2][len(args):])[:5]
 steps = args[5] if len(args) > 5 else 30
@@ -52,6 +71,8 @@ cfg = {"capacity_factor": 1, "drop_tokens": 1, "expert_top_k": topk,
        "sequence_len": S, "torch_dtype": dtype_code, "vocab_size": 32000}
 if n_shared:
     cfg["num_shared_experts"] = n_shared
+if router:
+    cfg.update(ROUTERS[router])
 f = tempfile.NamedTemporaryFile("w", suffix=".json", delete=False)
 json.dump(cfg, f)
 f.close()
@@ -62,6 +83,11 @@ adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
 x = torch.randn(1, S, H, dtype=adt, device="cuda")
 gw = torch.randn(H, E, dtype=adt, device="cuda")
+if router:
+    gw = (gw.float() / H ** 0.5).to(adt)
+    if router in ("v3", "sigmoid"):
+        score_bias = 0.1 * torch.randn(E, dtype=torch.float32, device="cuda")
+        moe.set_score_bias(score_bias)
 ew_all = torch.randn(E + n_shared + n_compose, expert_mats(hidden_act), P, H,
                      dtype=torch.float32, device="cuda").to(wdt)
 ew = ew_all[:E + n_shared]  # what moe_forward sees (a leading slice)
@@ -110,7 +136,8 @@ print(json.dumps({
     "workload": (f"1xMI355X S={S} H={H} P={P} E={E} top-{topk} "
                  f"dtype{dtype_code} act{hidden_act} CF=1 drop"
                  + (f" shared={n_shared}" if n_shared else "")
-                 + (f" compose={n_compose}" if n_compose else "")),
+                 + (f" compose={n_compose}" if n_compose else "")
+                 + (f" router={router}" if router else "")),
     "us_per_fwd": round(dt * 1e6, 1),
     "tokens_per_s": round(S / dt),
     "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
