@@ -73,6 +73,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_get_num_shared_experts.restype = ctypes.c_int
     lib.fm_last_forward_fused.argtypes = []
     lib.fm_last_forward_fused.restype = ctypes.c_int
+    lib.fm_last_forward_decode_ffn.argtypes = []
+    lib.fm_last_forward_decode_ffn.restype = ctypes.c_int
     lib.fm_moe_forward.argtypes = [p, p, p, p, p, p, p, p, i64]
     lib.fm_moe_forward.restype = ctypes.c_int
     lib.fm_moe_forward_phased.argtypes = [p, p, p, p, p, p, p, p, i64,

@@ -151,6 +151,35 @@ def _validate_router(cfg: dict) -> None:
             "routed_scaling_factor work at every num_experts")
 
 
+def num_tokens(cfg: dict) -> int:
+    """S, the token count of one forward: sequence_len * mini_batch."""
+    return cfg["sequence_len"] * cfg["mini_batch"]
+
+
+def _validate_tokens(cfg: dict) -> None:
+    """S = sequence_len * mini_batch is in 1..127 (decode-sized) or a
+    positive multiple of 128, and the decode refusals that the config alone
+    decides (world_size > 1 is refused at initialize)."""
+    for key in ("sequence_len", "mini_batch"):
+        v = cfg[key]
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{key} must be an integer; got {v!r}")
+    S = num_tokens(cfg)
+    if S < 1 or (S >= 128 and S % 128):
+        raise ValueError(
+            f"sequence_len * mini_batch = {S} must be in [1, 127] or a "
+            "positive multiple of 128")
+    if S < 128:
+        if cfg["torch_dtype"] == 5:
+            raise ValueError(
+                f"torch_dtype=5 (MX fp8) is not supported with sequence_len * "
+                f"mini_batch = {S} < 128 (decode-sized forwards)")
+        if cfg["is_training"]:
+            raise ValueError(
+                f"is_training=1 is not supported with sequence_len * "
+                f"mini_batch = {S} < 128 (decode-sized forwards)")
+
+
 def load_config(path: str | None = None) -> dict:
     path = path or DEFAULT_CONFIG_PATH
     with open(path) as f:
@@ -158,8 +187,7 @@ def load_config(path: str | None = None) -> dict:
     missing = [k for k in REQUIRED_KEYS if k not in cfg]
     if missing:
         raise ValueError(f"config {path} missing required keys: {missing}")
-    if cfg["sequence_len"] % 128:
-        raise ValueError("sequence_len must be a multiple of 128 (schema)")
+    _validate_tokens(cfg)
     if cfg["hidden_size"] % 64 or cfg["intermediate_size"] % 64:
         raise ValueError("hidden_size/intermediate_size must be multiples of 64 (schema)")
     if cfg["hidden_act"] not in (0, 1, 2, 3):

@@ -155,7 +155,9 @@ template <> struct ETr<fp16> {
 // gate.cuh:474-720).
 // ---------------------------------------------------------------------------
 
-template <typename T>
+// TAIL (decode-sized forwards, S < 128): rows >= S of the
+// one tile are neither read from x nor accumulated into logits32.
+template <typename T, bool TAIL = false>
 __global__ __launch_bounds__(256) void k_gate_logits(
     const T* __restrict__ x, const T* __restrict__ gate_w,
     float* __restrict__ logits32, uint32_t* __restrict__ eC, int S, int H,
@@ -195,6 +197,13 @@ __global__ __launch_bounds__(256) void k_gate_logits(
       for (int u = tid; u < unitsA; u += 256) {
         const int row = u / (BK / EPU);
         const int cu = u % (BK / EPU);
+        if constexpr (TAIL) {
+          if (m0 + row >= S) {
+            *reinterpret_cast<u32x4*>(aCh + row * LDA + cu * EPU) =
+                u32x4{0u, 0u, 0u, 0u};
+            continue;
+          }
+        }
         *reinterpret_cast<u32x4*>(aCh + row * LDA + cu * EPU) =
             *reinterpret_cast<const u32x4*>(x + (size_t)(m0 + row) * H + kc + cu * EPU);
       }
@@ -244,6 +253,9 @@ __global__ __launch_bounds__(256) void k_gate_logits(
     __syncthreads();
   }
   // one atomic per (token, expert) per H-chunk
+  if constexpr (TAIL) {
+    if (m0 + tok >= S) return;
+  }
   for (int e = e0; e < e1; ++e)
     atomicAdd(logits32 + (size_t)(m0 + tok) * E + eBase + e,
               part[tok * (Ec + 1) + e]);
@@ -349,7 +361,12 @@ __device__ __forceinline__ unsigned long long rv_group_taken(
   return taken;
 }
 
-template <typename T, int K, bool RV = false>
+// TAIL (decode-sized forwards, S < 128): the tile is
+// ragged. A row >= S is not read from logits32, selects the sentinel E in
+// every slot (the counting scan never counts it, so it adds nothing to eC)
+// and writes no gate_out row, kept entry or tokenIds entry. TAIL = false
+// compiles to the code it was.
+template <typename T, int K, bool RV = false, bool TAIL = false>
 __device__ __forceinline__ void route_tile_core(
     char* smem, float* __restrict__ logits32, T* __restrict__ gate_out,
     TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC,
@@ -381,6 +398,12 @@ __device__ __forceinline__ void route_tile_core(
   __syncthreads();  // prior pass's LDS readers done
   for (int i = tid; i < TT * E; i += 512) {
     const int row = i / E, col = i % E;
+    if constexpr (TAIL) {
+      if (pm0 + row >= S) {  // finite filler: the row's selections are void
+        logits[row * (E + 1) + col] = 0.0f;
+        continue;
+      }
+    }
     float* src = &logits32[(size_t)(pm0 + row) * E + col];
     logits[row * (E + 1) + col] = *src;
     *src = 0.0f;
@@ -428,7 +451,8 @@ __device__ __forceinline__ void route_tile_core(
       }
       if (li >= e0 && li < e1) takenM |= 1ull << (li - e0);
       if (sub == 0) {
-        sel[token * K + i] = (uint16_t)li;
+        sel[token * K + i] =
+            (TAIL && pm0 + token >= S) ? (uint16_t)E : (uint16_t)li;
         if (rp.selLogits) mCw += __expf(lv - m) * inv_d;
         else if (li < E) mCw += lrow[li];
       }
@@ -477,7 +501,8 @@ __device__ __forceinline__ void route_tile_core(
         }
         if (li >= e0 && li < e1) takenM |= 1ull << (li - e0);
         if (sub == 0) {
-          sel[token * K + i] = (uint16_t)li;
+          sel[token * K + i] =
+              (TAIL && pm0 + token >= S) ? (uint16_t)E : (uint16_t)li;
           mCw += __expf(lv - m) * inv_d;
         }
       }
@@ -489,6 +514,9 @@ __device__ __forceinline__ void route_tile_core(
   // per-token scalar store pattern was one cache line per element)
   for (int i = tid * 8; i < TT * PX; i += 512 * 8) {
     const int row = i / PX, col0 = i % PX;
+    if constexpr (TAIL) {
+      if (pm0 + row >= S) continue;
+    }
     const float mR = sMax[row], ivR = sInv[row];
     const float* lrow = logits + row * (E + 1);
     struct __attribute__((aligned(16))) V8 { T x[8]; } v;
@@ -534,7 +562,7 @@ __device__ __forceinline__ void route_tile_core(
     }
   }
   __syncthreads();
-  if (tid < TT) {
+  if (tid < TT && (!TAIL || pm0 + tid < S)) {
 #pragma unroll
     for (int i = 0; i < K; ++i) {
       const int e = sel[tid * K + i];
@@ -558,7 +586,7 @@ __device__ __forceinline__ void route_tile_core(
   }  // pass loop
 }
 
-template <typename T, int K, bool RV = false>
+template <typename T, int K, bool RV = false, bool TAIL = false>
 __global__ __launch_bounds__(512) void k_gate_route(
     float* __restrict__ logits32, T* __restrict__ gate_out,
     TPS* __restrict__ tokenIds, uint32_t* __restrict__ eC, int S, int E,
@@ -568,8 +596,9 @@ __global__ __launch_bounds__(512) void k_gate_route(
   // 763-773; types.cuh:936-958). Null in inference mode.
   // rp: read by the RV instantiations only
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  route_tile_core<T, K, RV>(smem, logits32, gate_out, tokenIds, eC, kept, gML,
-                            gMeC, S, E, PX, EC, pEC, blockIdx.x * 128, rp);
+  route_tile_core<T, K, RV, TAIL>(smem, logits32, gate_out, tokenIds, eC, kept,
+                                  gML, gMeC, S, E, PX, EC, pEC,
+                                  blockIdx.x * 128, rp);
 }
 
 // ---------------------------------------------------------------------------
@@ -1109,7 +1138,8 @@ __device__ __forceinline__ float gate_act(float v, int act) {
 typedef __attribute__((address_space(1))) const uint32_t gas_u32;
 typedef __attribute__((address_space(3))) uint32_t las_u32;
 
-template <typename ET, int PHASE, int ACT, bool HAS_BIAS, typename WET = ET>
+template <typename ET, int PHASE, int ACT, bool HAS_BIAS, typename WET = ET,
+          bool TAILA = false>
 __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
   using vec8 = typename ETr<ET>::vec8;
   constexpr int BM = 128, BN = 128, BK = 64;
@@ -1203,8 +1233,11 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
     for (int i = 0; i < 4; ++i) {
       const int grp = wave * 4 + i;
       const int row = grp * 8 + grow8;
-      const size_t arow = (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
-                                       : (size_t)(m0 + row);
+      size_t arow = (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
+                                 : (size_t)(m0 + row);
+      // TAILA: the logits GEMM of a decode-sized forward reads the
+      // caller's x, which ends at row nRows < BM
+      if constexpr (TAILA) arow = min(arow, (size_t)routed - 1);
       const ET* asrc = Ag + aBase + arow * aRowStride + kt + schunk * 8;
       __builtin_amdgcn_global_load_lds(
           (gas_u32*)asrc, (las_u32*)(Alds + grp * 512), 16, 0, 0);
@@ -2590,6 +2623,263 @@ __global__ __launch_bounds__(256) void k_group_gemm_f32(GemmArgs a) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// Weight-streaming expert FFN for decode-sized forwards (S < 128, bf16 /
+// fp16 / fp8 weights). An expert sees a handful of rows,
+// so the forward is bound by streaming the weights of the experts that were
+// hit once. One block = 16 weight rows (output columns) of one z-slice; its
+// four waves split K in interleaved 128-element chunks and sum their
+// partials through LDS in wave order (no atomics: the result is a pure
+// function of the inputs). A slice without rows returns before it touches a
+// weight.
+//   weights      straight from global memory into the MFMA B fragment, 16 B
+//                per lane, K-contiguous (fp8: 16 bytes = two K-steps of one
+//                lane, dequantised at fragment use); the next chunk's loads
+//                are issued before the current chunk is consumed (two named
+//                register sets, so the compiler's waits stay counted)
+//   activations  the expert's rows (x gathered through tokenIds, or xM) are
+//                L2-resident and re-read by every block of the slice: each
+//                wave stages its chunk in full 256-B row pieces into its own
+//                LDS region and reads A fragments with 16-B LDS loads
+//   rows         up to kDecRows = 32 per pass (two 16-row fragments sharing
+//                each loaded B fragment); more rows take further passes
+// PHASE 0 (up; GATED streams the Wglu and Wup rows of the same P range and
+// stores act(g) * u), PHASE 1 (down) with the combine epilogue of
+// gemm_job_body PHASE 1. Consumes the same GemmArgs routing metadata; N is
+// the plain output width (P or H) and gluOffset the Wup -> Wglu distance.
+// ---------------------------------------------------------------------------
+constexpr int kDecBK = 128;          // K elements per staged chunk
+constexpr int kDecLDA = kDecBK + 8;  // LDS row pitch in elements (272 B)
+constexpr int kDecRows = 32;         // rows per pass
+// unset FM_DECODE_FFN: the streaming kernels are the default up to the
+// largest S at which every one of their measured runs beat every run of the
+// grouped GEMMs on all three model shapes (DESIGN.md par.5k has the A/B):
+// bf16 S <= 4, fp16 S <= 8 (measured at 1, 2, 4, 8), fp8 weights S <= 16.
+// Above, the default stays the grouped GEMMs.
+constexpr int kDecodeFfnMaxSBf16 = 4;
+constexpr int kDecodeFfnMaxSFp16 = 8;
+constexpr int kDecodeFfnMaxSFp8 = 16;
+
+template <typename ET, typename WET, int PHASE, bool GATED>
+__global__ __launch_bounds__(256) void k_decode_ffn(GemmArgs a) {
+  using vec8 = typename ETr<ET>::vec8;
+  constexpr int BEZ = (int)sizeof(WET);
+  constexpr int KPL = 16 / BEZ;               // K elements per 16-B load
+  constexpr int NLD = kDecBK / (4 * KPL);     // loads per chunk and matrix
+  constexpr int NM = GATED ? 2 : 1;           // 0: Wup (or the one matrix)
+  constexpr int kArena = 4 * kDecRows * kDecLDA * 2;
+  __shared__ __attribute__((aligned(16))) char smem[128 * 8 + kArena];
+  TPS* sTps = reinterpret_cast<TPS*>(smem);
+  f32x4* red = reinterpret_cast<f32x4*>(smem + 128 * 8);  // overlays A
+
+  const int e = blockIdx.y;
+  const uint32_t routed = min(a.eC[e], (uint32_t)min(a.EC, 128));
+  if (routed == 0) return;  // before any weight is touched
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int q = lane >> 4;    // K sub-range of the lane within a load
+  const int rl = lane & 15;   // fragment row (A) / weight row (B)
+  const int K = a.K, N = a.N;
+  const int n0 = blockIdx.x * 16;
+  const int we = a.segExpert ? a.segExpert[e] : e;  // weight / bias expert
+  ET* Aw = reinterpret_cast<ET*>(smem + 128 * 8) + wave * kDecRows * kDecLDA;
+
+  if (tid < 128) {
+    TPS t{0u, 1.0f};
+    if ((uint32_t)tid < routed) t = a.tokenIds[(size_t)e * a.pEC + tid];
+    sTps[tid] = t;
+  }
+  __syncthreads();
+
+  const ET* __restrict__ Ag = reinterpret_cast<const ET*>(a.A) +
+                              (PHASE == 0 ? (size_t)0
+                                          : (size_t)e * a.strideAExpert);
+  const WET* __restrict__ Bw[NM];
+  Bw[0] = reinterpret_cast<const WET*>(a.B) + (size_t)we * a.strideBExpert +
+          (size_t)(n0 + rl) * K + q * KPL;
+  if constexpr (GATED) Bw[1] = Bw[0] + a.gluOffset;
+
+  for (int mg0 = 0; mg0 < (int)routed; mg0 += kDecRows) {
+    const int rp = min((int)routed - mg0, kDecRows);
+    const bool two = rp > 16;  // a second 16-row fragment
+    // A staging: 16 lanes x 16 B = one 256-B row piece, 4 rows per
+    // instruction; element offset of the lane's piece, -1 past the rows
+    int aOff[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int r = i * 4 + q;
+      const int m = mg0 + r;
+      aOff[i] = r < rp ? (PHASE == 0
+                              ? (int)tpsTok(sTps[m].tokenIdx) * a.H
+                              : m * K) + rl * 8
+                       : -1;
+    }
+    f32x4 acc[NM][2];
+#pragma unroll
+    for (int mt = 0; mt < NM; ++mt)
+#pragma unroll
+      for (int f = 0; f < 2; ++f) acc[mt][f] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    u32x4 areg[8];
+    auto loadA = [&](int kc) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (i >= 4 && !two) break;
+        areg[i] = u32x4{0u, 0u, 0u, 0u};
+        if (aOff[i] >= 0 && kc + rl * 8 < K)
+          areg[i] = *reinterpret_cast<const u32x4*>(Ag + aOff[i] + kc);
+      }
+    };
+    auto storeA = [&]() __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        if (i >= 4 && !two) break;
+        *reinterpret_cast<u32x4*>(Aw + (i * 4 + q) * kDecLDA + rl * 8) =
+            areg[i];
+      }
+    };
+    auto loadB = [&](u32x4 (&b)[NM][NLD], int kc) __attribute__((always_inline)) {
+#pragma unroll
+      for (int mt = 0; mt < NM; ++mt)
+#pragma unroll
+        for (int j = 0; j < NLD; ++j) {
+          const int k = kc + j * 4 * KPL;  // wave-uniform; K % 64 == 0
+          b[mt][j] = u32x4{0u, 0u, 0u, 0u};
+          if (k < K) b[mt][j] = *reinterpret_cast<const u32x4*>(Bw[mt] + k);
+        }
+    };
+    auto compute = [&](const u32x4 (&b)[NM][NLD]) __attribute__((always_inline)) {
+#pragma unroll
+      for (int j = 0; j < NLD; ++j)
+#pragma unroll
+        for (int s = 0; s < KPL / 8; ++s) {
+          const int ko = j * 4 * KPL + q * KPL + s * 8;
+          const vec8 a0 =
+              *reinterpret_cast<const vec8*>(Aw + rl * kDecLDA + ko);
+          vec8 a1 = a0;
+          if (two)
+            a1 = *reinterpret_cast<const vec8*>(Aw + (16 + rl) * kDecLDA + ko);
+#pragma unroll
+          for (int mt = 0; mt < NM; ++mt) {
+            vec8 bf;
+            if constexpr (BEZ == 1)
+              bf = dequant_fp8x8_bf16(b[mt][j][2 * s], b[mt][j][2 * s + 1]);
+            else
+              bf = __builtin_bit_cast(vec8, b[mt][j]);
+            acc[mt][0] = ETr<ET>::mfma(a0, bf, acc[mt][0]);
+            if (two) acc[mt][1] = ETr<ET>::mfma(a1, bf, acc[mt][1]);
+          }
+        }
+    };
+    // the A region is private to the wave: LDS serves a wave's accesses in
+    // order, so a wavefront-scope fence orders its stores and fragment reads
+    auto waveSync = [&]() __attribute__((always_inline)) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    };
+    // consume chunk kc from bc; prefetch chunk kc + 4 * kDecBK into bn
+    auto step = [&](const u32x4 (&bc)[NM][NLD], u32x4 (&bn)[NM][NLD],
+                    int kc) __attribute__((always_inline)) {
+      const int kn = kc + 4 * kDecBK;
+      const bool more = kn < K;
+      if (more) {
+        loadA(kn);
+        loadB(bn, kn);
+      }
+      compute(bc);
+      if (more) {
+        waveSync();
+        storeA();
+        waveSync();
+      }
+    };
+    u32x4 b0[NM][NLD], b1[NM][NLD];
+    const int kc0 = wave * kDecBK;
+    if (kc0 < K) {
+      loadA(kc0);
+      loadB(b0, kc0);
+      storeA();
+      waveSync();
+      for (int kc = kc0; kc < K; kc += 8 * kDecBK) {
+        step(b0, b1, kc);
+        if (kc + 4 * kDecBK < K) step(b1, b0, kc + 4 * kDecBK);
+      }
+    }
+
+    // fixed-order K reduction: waves 1..3 -> LDS, wave 0 sums and stores
+    __syncthreads();  // every wave is done with its A region
+    if (wave > 0) {
+#pragma unroll
+      for (int mt = 0; mt < NM; ++mt)
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+          red[(((wave - 1) * NM + mt) * 2 + f) * 64 + lane] = acc[mt][f];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int w = 0; w < 3; ++w)
+#pragma unroll
+        for (int mt = 0; mt < NM; ++mt)
+#pragma unroll
+          for (int f = 0; f < 2; ++f)
+            acc[mt][f] += red[((w * NM + mt) * 2 + f) * 64 + lane];
+      // C/D map of the 16x16 MFMA: col = lane & 15, row = (lane >> 4) * 4 + r
+      const int col = n0 + rl;
+      float bv = 0.0f;
+      if (a.bias)
+        bv = toF(reinterpret_cast<const ET*>(a.bias)[(size_t)we * N + col]);
+      const bool multi = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+      const bool scaled =
+          (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+      const int nSlot = a.topk + a.nShared;
+#pragma unroll
+      for (int f = 0; f < 2; ++f) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = f * 16 + q * 4 + r;
+          if (row >= rp) continue;
+          const int m = mg0 + row;
+          if constexpr (PHASE == 0) {
+            float v;
+            if constexpr (GATED) {
+              v = gate_act(acc[1][f][r], a.act) * acc[0][f][r];
+            } else {
+              v = acc[0][f][r] + bv;
+              v = (a.act == 0)
+                      ? fmaxf(v, 0.0f)
+                      : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+            }
+            reinterpret_cast<ET*>(a.out)[(size_t)e * a.strideOExpert +
+                                         (size_t)m * N + col] =
+                ETr<ET>::fromf(v);
+          } else {
+            const TPS tp = sTps[m];
+            const uint32_t tok = tpsTok(tp.tokenIdx);
+            const float v = acc[0][f][r] + bv;
+            if (multi) {
+              float sc = 1.0f;
+              if (scaled)
+                sc = toF(reinterpret_cast<const ET*>(
+                         a.gate_out)[(size_t)tok * a.PX + a.expertOffset + e]) /
+                     tp.probSum;
+              reinterpret_cast<ET*>(a.O32)[
+                  ((size_t)tok * nSlot + tpsJ(tp.tokenIdx)) * a.H + col] =
+                  ETr<ET>::fromf(v * sc);
+            } else {
+              reinterpret_cast<ET*>(a.moe_out)[(size_t)tok * a.H + col] =
+                  ETr<ET>::fromf(v);
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // the next pass restages over the reduction slabs
+  }
+}
+
 // sum the k non-atomic combine slots (kept-masked) into the output
 // (k>1 path; replaces the fp32-atomic accumulator + cast). Blocks walk
 // token groups, 16-B vector loads per slot (a scalar grid-stride
@@ -3493,6 +3783,7 @@ struct State {
   int nCU = 0;
   int wallClockKHz = 100000;      // s_memrealtime rate (ticks per ms)
   bool lastForwardFused = false;
+  bool lastForwardDecodeFfn = false;  // the last forward took k_decode_ffn
   // router variant (fm_set_router); reset with the State
   fm_router_config router{0, 1, 1, 1, 0, 1.0f, nullptr};
   bool routerRV = false;    // any non-default field: the RV gate kernels
@@ -3561,8 +3852,9 @@ static bool gateFusedEnabled() {
 
 // does launch_gate take the single-launch k_gate_fused?
 static bool gateFusedApplies() {
-  return g.gateCtl && g.esz == 2 && g.E <= 64 && !g.cfg.is_training &&
-         gateFusedEnabled();
+  // (never at a decode size: k_gate_fused has no ragged tile)
+  return g.gateCtl && g.S >= 128 && g.esz == 2 && g.E <= 64 &&
+         !g.cfg.is_training && gateFusedEnabled();
 }
 
 // sub-block token count of k_gate_fused (16 -> 256 threads, S/16 blocks;
@@ -3617,7 +3909,10 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
                : launch_gate_fused<bf16>(st, x, gate_w, gate_out, S);
   // split gate: logits GEMM parallelised over (token tile, H chunk),
   // then per-tile softmax/top-k/route (see k_gate_logits/k_gate_route)
-  const int tiles = (int)(S / 128);
+  // a decode-sized forward (S < 128) is one ragged tile:
+  // the TAIL instantiations mask its rows >= S
+  const int tiles = (int)DIVUP(S, 128);
+  const bool tail = S < 128;
   int chunksWanted = DIVUP(512, tiles);
   int Hc = DIVUP(DIVUP(g.H, chunksWanted), 64) * 64;
   const int chunks = DIVUP(g.H, Hc);
@@ -3639,32 +3934,37 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
   float* gMeCp = g.cfg.is_training ? g.gMeC : nullptr;
   if (g.cfg.is_training)
     FM_HIP_CHECK(hipMemsetAsync(g.gML, 0, 2 * (size_t)g.E * sizeof(float), st));
-#define GATE_LOGITS(T)                                                        \
+#define GATE_LOGITS_T(T, TL)                                                  \
   do {                                                                        \
     if (ldsL > 64 * 1024)                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gate_logits<T>),   \
-                          hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                          (int)ldsL);                                         \
-    hipLaunchKernelGGL((k_gate_logits<T>), dim3(tiles, chunks, eChunks),     \
+      (void)hipFuncSetAttribute(                                              \
+          reinterpret_cast<const void*>(&k_gate_logits<T, TL>),               \
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsL);             \
+    hipLaunchKernelGGL((k_gate_logits<T, TL>), dim3(tiles, chunks, eChunks),  \
                        dim3(256), ldsL, st, reinterpret_cast<const T*>(x),    \
                        reinterpret_cast<const T*>(gate_w), g.logits32, g.eC,  \
                        (int)S, g.H, g.E, Hc);                                 \
   } while (0)
-#define GATE_ROUTE_RV(T, KK, RVV)                                             \
+#define GATE_LOGITS(T) GATE_LOGITS_T(T, false)
+#define GATE_ROUTE_RV(T, KK, RVV, TL)                                         \
   do {                                                                        \
     if (ldsR > 64 * 1024)                                                     \
       (void)hipFuncSetAttribute(                                                    \
-          reinterpret_cast<const void*>(&k_gate_route<T, KK, RVV>),           \
+          reinterpret_cast<const void*>(&k_gate_route<T, KK, RVV, TL>),       \
           hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsR);             \
-    hipLaunchKernelGGL((k_gate_route<T, KK, RVV>), dim3(tiles), dim3(512),    \
-                       ldsR, st, g.logits32, reinterpret_cast<T*>(gate_out),  \
-                       g.tokenIds, g.eC, (int)S, g.E, g.PX, g.EC, g.pEC,      \
-                       gMLp, gMeCp, g.kept, rp);                              \
+    hipLaunchKernelGGL((k_gate_route<T, KK, RVV, TL>), dim3(tiles),           \
+                       dim3(512), ldsR, st, g.logits32,                       \
+                       reinterpret_cast<T*>(gate_out), g.tokenIds, g.eC,      \
+                       (int)S, g.E, g.PX, g.EC, g.pEC, gMLp, gMeCp, g.kept,   \
+                       rp);                                                   \
   } while (0)
 #define GATE_ROUTE(T, KK)                                                     \
   do {                                                                        \
-    if (g.routerRV) { GATE_ROUTE_RV(T, KK, true); }                           \
-    else { GATE_ROUTE_RV(T, KK, false); }                                     \
+    if (tail) {                                                               \
+      if (g.routerRV) { GATE_ROUTE_RV(T, KK, true, true); }                   \
+      else { GATE_ROUTE_RV(T, KK, false, true); }                             \
+    } else if (g.routerRV) { GATE_ROUTE_RV(T, KK, true, false); }             \
+    else { GATE_ROUTE_RV(T, KK, false, false); }                              \
   } while (0)
 #define GATE_K(T)                                                             \
   switch (g.cfg.expert_top_k) {                                               \
@@ -3701,13 +4001,15 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
     if (!mfmaLogits) GATE_LOGITS(fp16);
     GATE_K(fp16)
   } else {
-    GATE_LOGITS(float);
+    if (tail) GATE_LOGITS_T(float, true);
+    else GATE_LOGITS(float);
     GATE_K(float)
   }
 #undef GATE_K
 #undef GATE_ROUTE
 #undef GATE_ROUTE_RV
 #undef GATE_LOGITS
+#undef GATE_LOGITS_T
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
 }
@@ -4105,11 +4407,26 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
     setErr("world_size > 64 not supported");
     return FM_ERR_UNSUPPORTED;
   }
-  if (g.S < 128 || g.S % 128) {
-    // the gate tiles tokens in blocks of 128 (launch_gate: tiles = S/128);
-    // a ragged tail would be silently dropped - reject instead
-    setErr("S = sequence_len * mini_batch must be a positive multiple of 128");
+  if (g.S < 1 || (g.S >= 128 && g.S % 128)) {
+    // the gate tiles tokens in blocks of 128 (launch_gate); the one ragged
+    // tile it masks is the decode-sized forward, S < 128 (DESIGN.md
+    // par.5k). A ragged tail behind full tiles is rejected.
+    snprintf(g_err, sizeof(g_err),
+             "S = sequence_len * mini_batch = %d must be in [1, 127] or a "
+             "positive multiple of 128", g.S);
     return FM_ERR_SHAPE;
+  }
+  if (g.S < 128) {
+    // decode-sized forwards: inference on one rank, never MX
+    const char* key = cfg->dtype == 5 ? "torch_dtype 5 (MX)"
+                      : cfg->is_training ? "is_training 1"
+                      : world_size > 1 ? "world_size > 1" : nullptr;
+    if (key) {
+      snprintf(g_err, sizeof(g_err),
+               "%s is not supported with S = sequence_len * mini_batch = %d "
+               "< 128 (decode-sized forwards)", key, g.S);
+      return FM_ERR_UNSUPPORTED;
+    }
   }
   if (cfg->expert_top_k < 1 || cfg->expert_top_k > 8 ||
       cfg->expert_top_k > g.E) {
@@ -4133,8 +4450,11 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   g.nLxAlloc += g.nV;  // xM: one [pEC, P] slice per virtual slice (world 1)
   const int nZ = g.E + g.nV;
   FM_HIP_CHECK(hipMalloc(&g.tokenIds, (size_t)nZ * g.pEC * sizeof(TPS)));
-  FM_HIP_CHECK(hipMalloc(&g.logits32, (size_t)g.S * g.E * sizeof(float)));
-  FM_HIP_CHECK(hipMemset(g.logits32, 0, (size_t)g.S * g.E * sizeof(float)));
+  // what the gate kernels index by 128-row tile is sized in whole tiles
+  // (S < 128 is one ragged tile; its rows >= S stay untouched)
+  const size_t sTile = (size_t)DIVUP(g.S, 128) * 128;
+  FM_HIP_CHECK(hipMalloc(&g.logits32, sTile * g.E * sizeof(float)));
+  FM_HIP_CHECK(hipMemset(g.logits32, 0, sTile * g.E * sizeof(float)));
   FM_HIP_CHECK(hipMalloc(&g.gML, 2 * (size_t)g.E * sizeof(float)));
   g.gMeC = g.gML + g.E;
   FM_HIP_CHECK(hipMalloc(&g.eC, (size_t)nZ * sizeof(uint32_t)));
@@ -4178,8 +4498,8 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   // combine slots [S, k + nSh, H]; kept stays [S, k] (gate-written, stride k)
   FM_HIP_CHECK(hipMalloc(&g.cbuf, (size_t)g.S * (g.cfg.expert_top_k + g.nSh) *
                                       g.H * g.esz));
-  FM_HIP_CHECK(hipMalloc(&g.kept, (size_t)g.S * g.cfg.expert_top_k));
-  if (g.esz == 2 && g.E <= 64 && !g.cfg.is_training) {
+  FM_HIP_CHECK(hipMalloc(&g.kept, sTile * g.cfg.expert_top_k));
+  if (g.S >= 128 && g.esz == 2 && g.E <= 64 && !g.cfg.is_training) {
     // k_gate_fused workspace; the ticket words are zeroed here once and
     // left zero by every launch (no memset node per forward)
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
@@ -4282,6 +4602,10 @@ int fm_get_num_shared_experts(void) { return g.initialized ? g.nSh : -1; }
 
 int fm_last_forward_fused(void) {
   return g.initialized ? (g.lastForwardFused ? 1 : 0) : -1;
+}
+
+int fm_last_forward_decode_ffn(void) {
+  return g.initialized ? (g.lastForwardDecodeFfn ? 1 : 0) : -1;
 }
 
 int fm_set_router(const fm_router_config* r) {
@@ -4540,7 +4864,9 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
       // big-E shapes (e.g. cfg5: S=16384, E=256) fill the chip with the
       // pipelined 128x128 tile (zeroing of eC still needs the small
       // kernel's block-0 path, so hand that to a tiny memset instead)
-      if (mode != 2 && N >= 128) {
+      // (a decode-sized forward, M < 128, always takes the small kernel:
+      // its TAILA instantiation clamps the ragged x rows)
+      if (mode != 2 && N >= 128 && M >= 128) {
         GemmArgs a3 = a;
         a3.splitK = 1;
         a3.noRemap = noRemap;
@@ -4593,7 +4919,13 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
       // logits32 is zero on entry (zeroed at initialize and re-zeroed by
       // k_gate_route after each read)
       dim3 g3(DIVUP(M, 128), DIVUP(N, 128), sk3);
-      if (g.cfg.dtype == 3)
+      if (M < 128 && g.cfg.dtype == 3)
+        hipLaunchKernelGGL((k_group_gemm_bf16<fp16, 3, 0, false, fp16, true>),
+                           g3, dim3(256), 0, st, a3);
+      else if (M < 128)
+        hipLaunchKernelGGL((k_group_gemm_bf16<bf16, 3, 0, false, bf16, true>),
+                           g3, dim3(256), 0, st, a3);
+      else if (g.cfg.dtype == 3)
         hipLaunchKernelGGL((k_group_gemm_bf16<fp16, 3, 0, false>), g3,
                            dim3(256), 0, st, a3);
       else
@@ -4696,6 +5028,56 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
   return FM_OK;
 }
 
+// FM_DECODE_FFN: 0 forces the grouped GEMMs at a decode size, 1 forces the
+// weight-streaming kernels, unset takes the measured default. Re-read per
+// call (tests toggle it) and part of the graph key, like FM_FUSED.
+static int decodeFfnMode() {
+  const char* e = getenv("FM_DECODE_FFN");
+  return (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1;
+}
+
+// does a forward take k_decode_ffn? Only below 128 tokens, and only for the
+// 2-byte activation families (fp32 stays on k_group_gemm_f32).
+static bool decodeFfnApplies() {
+  if (g.S >= 128 || g.esz != 2 || g.cfg.dtype == 5) return false;
+  const int m = decodeFfnMode();
+  if (m >= 0) return m == 1;
+  return g.S <= (g.cfg.dtype == 4   ? kDecodeFfnMaxSFp8
+                 : g.cfg.dtype == 3 ? kDecodeFfnMaxSFp16
+                                    : kDecodeFfnMaxSBf16);
+}
+
+// one launch of k_decode_ffn over all z-slices: 16 weight rows per block
+static int launch_decode_ffn(hipStream_t st, int phase, const GemmArgs& a,
+                             int nZ) {
+  const bool gated = phase == 0 && a.act >= 2;
+  if (gated && a.bias) {
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  GemmArgs aa = a;
+  aa.gluOffset = gated ? 2LL * a.N * a.K : 0;  // Wup (slot 0) -> Wglu (slot 2)
+  const dim3 grid(a.N / 16, nZ), block(256);
+#define DEC_ET(ET, WET)                                                       \
+  do {                                                                        \
+    if (phase == 1)                                                           \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 1, false>), grid, block, 0,   \
+                         st, aa);                                             \
+    else if (gated)                                                           \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, true>), grid, block, 0,    \
+                         st, aa);                                             \
+    else                                                                      \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, false>), grid, block, 0,   \
+                         st, aa);                                             \
+  } while (0)
+  if (g.cfg.dtype == 3) DEC_ET(fp16, fp16);
+  else if (g.cfg.dtype == 4) DEC_ET(bf16, fp8e4m3);
+  else DEC_ET(bf16, bf16);
+#undef DEC_ET
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
 static int launch_cast_combine(hipStream_t st, void* moe_out) {
   // tokens per block iteration (mirrors the kernel): H / (16 / esz) chunks
   const int cpt = std::max(1, g.H / (16 / (int)g.esz));
@@ -4770,6 +5152,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // fused single-launch path (the north-star structure); classic
   // multi-kernel path remains for fp32 and as FM_FUSED=0 fallback
   g.lastForwardFused = false;
+  g.lastForwardDecodeFfn = false;
   if (b_up && g.gated) {  // refuse before anything is enqueued
     setErr("b_up is not supported with a gated hidden_act (2/3)");
     return FM_ERR_UNSUPPORTED;
@@ -4779,8 +5162,9 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // (nor do configs with shared experts: the fused walks know E experts)
   // (nor does a non-default router: k_moe_fused routes with the legacy
   // route_tile_core)
-  if (fusedEnabled() && g.esz == 2 && g.world == 1 && g.cfg.dtype != 5 &&
-      !g.gated && g.nSh == 0 && !g.routerRV) {
+  // (nor does a decode-sized forward, S < 128: no ragged tile there)
+  if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
+      g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -4842,7 +5226,11 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
     up.out8 = g.xM8;       // 256-tile up epilogue quantizes in-register
     up.outScales = g.xMs;  // (skips the separate k_quant_mx xM pass)
   }
-  rc = launch_group_gemm(st, 0, up, g.pEC, nZ);
+  // decode-sized forward: the weight-streaming kernels (par.5k)
+  const bool decode = decodeFfnApplies();
+  g.lastForwardDecodeFfn = decode;
+  rc = decode ? launch_decode_ffn(st, 0, up, nZ)
+              : launch_group_gemm(st, 0, up, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[3], st));
 
@@ -4865,7 +5253,8 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   dn.moe_out = moe_out;
   dn.strideAExpert = (long long)g.pEC * g.P;
   dn.K = g.P; dn.N = g.H;
-  rc = launch_group_gemm(st, 1, dn, g.pEC, nZ);
+  rc = decode ? launch_decode_ffn(st, 1, dn, nZ)
+              : launch_group_gemm(st, 1, dn, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[4], st));
 
@@ -4898,8 +5287,9 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                   const_cast<void*>(expert_w), const_cast<void*>(b_up),
                   const_cast<void*>(b_dn), gate_out, moe_out,
                   reinterpret_cast<void*>(static_cast<uintptr_t>(
-                      (uint64_t)g.routerGen << 40 | (uint64_t)S << 2 |
-                      (gateFusedEnabled() ? 2 : 0) |
+                      (uint64_t)g.routerGen << 40 |
+                      (uint64_t)(decodeFfnMode() + 1) << 38 |
+                      (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
                       (fusedEnabled() ? 1 : 0)))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;

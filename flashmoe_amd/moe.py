@@ -10,7 +10,8 @@ import os
 
 from . import _ext
 from .config import (MAX_VARIANT_EXPERTS, element_size_of, expert_mats,
-                     load_config, num_shared, router_is_default, router_of,
+                     load_config, num_shared, num_tokens, router_is_default,
+                     router_of,
                      torch_dtype_of, weight_dtype_of)
 
 _state = {
@@ -77,7 +78,7 @@ def initialize(config_path: str | None = None, rank: int | None = None,
             _state.update(initialized=False, cfg=None)
             raise
     # persistent gate_out buffer
-    S = cfg["sequence_len"] * cfg["mini_batch"]
+    S = num_tokens(cfg)
     PX = (cfg["num_experts"] + 63) // 64 * 64
     _state["gate_out"] = torch.empty(
         S, PX, dtype=torch_dtype_of(cfg["torch_dtype"]), device="cuda"
@@ -165,7 +166,7 @@ def get_compiled_config() -> dict:
         # the reference reads compile-time constants without initialize;
         # we read the default config file (same contract)
         cfg = load_config()
-        S = cfg["sequence_len"] * cfg["mini_batch"]
+        S = num_tokens(cfg)
         return {
             "S": S,
             "H": cfg["hidden_size"],

@@ -73,6 +73,25 @@ extern "C" {
  * FM_ERR_UNSUPPORTED at fm_initialize: nSh outside 0..4, expert_top_k +
  * nSh > 16, nSh > 0 with dtype 5, nSh > 0 with world_size > 1.
  *
+ * DECODE-SIZED FORWARDS: S = sequence_len * mini_batch may be any integer in
+ * 1..127 as well as a positive multiple of 128 (the rule is on the product:
+ * sequence_len 1, mini_batch 8 is the natural decode config). One config is
+ * one S. Below 128 the gate runs as one masked tile (rows >= S are neither
+ * read nor written, so gate_out is exactly [S, PX] and moe_out exactly
+ * [S, H]; the placement is deterministic, overflow included). For dtype
+ * 2/3/4 there are weight-streaming expert FFN kernels that skip the weights
+ * of experts without rows; they are the default at S <= 4 (dtype 2), S <= 8
+ * (dtype 3) and S <= 16 (dtype 4), the grouped GEMMs above that
+ * (FM_DECODE_FFN=0 forces the grouped GEMMs, =1 the streaming kernels;
+ * re-read per call; fm_last_forward_decode_ffn() reports which ran). Supported: dtype 0-4, every
+ * hidden_act, b_up (ungated) / b_dn, top-1..8, drop and no-drop,
+ * num_shared_experts, every router variant; fm_moe_forward,
+ * fm_moe_forward_phased, fm_gate_forward, fm_read_routing, fm_export_routing.
+ * FM_ERR_UNSUPPORTED at fm_initialize with S < 128: dtype 5, is_training 1,
+ * world_size > 1. S >= 128 that is no multiple of 128: FM_ERR_SHAPE. A
+ * decode-sized forward never takes the single-launch kernels
+ * (fm_last_forward_fused() reports 0).
+ *
  * ABI NOTE: the struct GREW by this trailing field. A caller built against
  * the eleven-field layout must be rebuilt (or zero the new field). */
 typedef struct fm_config {
@@ -84,8 +103,10 @@ typedef struct fm_config {
   int32_t hidden_size;        /* H */
   int32_t intermediate_size;  /* P */
   int32_t sequence_len;  /* sequence_len * mini_batch (= S, the token
-                          * count) must be a positive multiple of 128:
-                          * the gate tiles tokens in blocks of 128 */
+                          * count) must be in 1..127 (decode-sized, see
+                          * above) or a positive multiple of 128: the gate
+                          * tiles tokens in blocks of 128 and masks at most
+                          * the one ragged tile of S < 128 */
   int32_t mini_batch;
   int32_t dtype;
   int32_t is_training;
@@ -166,6 +187,12 @@ int fm_get_num_shared_experts(void);
  * single-launch fused kernel, 0 if it ran the multi-kernel path, -1
  * before fm_initialize. */
 int fm_last_forward_fused(void);
+
+/* 1 if the last fm_moe_forward / fm_moe_forward_phased ran its expert FFN on
+ * the weight-streaming kernels of a decode-sized forward (k_decode_ffn), 0
+ * if it ran the grouped GEMMs (always at S >= 128 and for fp32), -1 before
+ * fm_initialize. */
+int fm_last_forward_decode_ffn(void);
 
 /* THE hot path. Replaces _C.moe_forward (python_bindings.cu:17-151) for
  * the single-rank case: gate -> route -> expert FFN -> combine on this
