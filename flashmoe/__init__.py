@@ -6,10 +6,13 @@ from flashmoe_amd import (  # noqa: F401
     get_compiled_config,
     get_num_local_experts,
     get_router,
+    get_weight_scales,
     initialize,
     moe_forward,
+    pack_weight_scales,
     run_moe,
     set_score_bias,
+    set_weight_scales,
 )
 from flashmoe_amd import moe as _C  # noqa: F401  (the _C-equivalent surface)
 

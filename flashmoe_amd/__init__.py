@@ -10,9 +10,12 @@ from .moe import (  # noqa: F401
     get_num_local_experts,
     get_num_shared_experts,
     get_router,
+    get_weight_scales,
     initialize,
     moe_forward,
+    pack_weight_scales,
     set_score_bias,
+    set_weight_scales,
 )
 from .ops import run_moe  # noqa: F401
 
@@ -27,4 +30,7 @@ __all__ = [
     "get_num_shared_experts",
     "set_score_bias",
     "get_router",
+    "set_weight_scales",
+    "get_weight_scales",
+    "pack_weight_scales",
 ]

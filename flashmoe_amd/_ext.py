@@ -61,6 +61,11 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_set_router.restype = ctypes.c_int
     lib.fm_get_router.argtypes = [ctypes.POINTER(FMRouterConfig)]
     lib.fm_get_router.restype = ctypes.c_int
+    lib.fm_set_weight_scales.argtypes = [p, ctypes.c_int32]
+    lib.fm_set_weight_scales.restype = ctypes.c_int
+    lib.fm_get_weight_scales.argtypes = [ctypes.POINTER(p),
+                                         ctypes.POINTER(ctypes.c_int32)]
+    lib.fm_get_weight_scales.restype = ctypes.c_int
     lib.fm_initialize.argtypes = [ctypes.POINTER(FMConfig), ctypes.c_int, ctypes.c_int]
     lib.fm_initialize.restype = ctypes.c_int
     lib.fm_finalize.argtypes = []

@@ -1121,7 +1121,24 @@ struct GemmArgs {
                              // a z-slice e >= nRoutedE is a shared-expert
                              // slice: scale 1, no gate_out read. Both are
                              // wave-uniform; 0 / unused without shared experts
+  const float* wScale;       // fp8 weights (dtype 4/5): per-output-channel
+  long long wScaleStride;    // fp32 scales of B's rows (fm_set_weight_scales)
+  int wScaleGlu;             // or null = 1.0. Indexed like the bias slabs:
+                             // wScale + we * wScaleStride is the [N] vector of
+                             // this phase's matrix (the host passes the
+                             // phase's base inside the per-expert record);
+                             // wScaleGlu is the distance from there to the
+                             // gating projection's vector (gated PHASE 0)
 };
+
+// Per-output-channel weight scale: W_eff[n, :] = s[n] *
+// W_fp8[n, :] factors out of the K sum, so the fp8-weight kernels multiply the
+// fp32 accumulator by s[n] in the epilogue, ahead of bias and activation. The
+// kernels test the pointer at run time; without scales the factor is 1.0f
+// and acc * 1.0f is acc, bit for bit.
+__device__ __forceinline__ float wscale_at(const float* sp, int col, int n) {
+  return (sp && col < n) ? sp[col] : 1.0f;
+}
 
 // Gated experts (hidden_act 2 SwiGLU, 3 GeGLU): h = act(g) * u with
 // g = x.Wglu^T, u = x.Wup^T, both still fp32 accumulators. The up GEMM
@@ -1337,6 +1354,29 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
       if (col < N) bv[ni] = toF(bptr[col]);
     }
   }
+  // fp8 weights: this job's per-column weight scales, loaded once beside bv
+  // (gated: sv[2j] is s_glu and sv[2j+1] is s_up of the same P column)
+  constexpr bool WS = (BEZ == 1) && (PHASE != 3);
+  float sv[4] = {1.f, 1.f, 1.f, 1.f};
+  if constexpr (WS) {
+    const float* sp =
+        a.wScale ? a.wScale + (size_t)we * a.wScaleStride : nullptr;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      if constexpr (GATED) {
+        const int col = (n0 >> 1) + wc * 32 + (ni >> 1) * 16 + cl;
+        sv[ni] = wscale_at(sp ? sp + ((ni & 1) ? 0 : a.wScaleGlu) : nullptr,
+                           col, N >> 1);
+      } else {
+        sv[ni] = wscale_at(sp, n0 + wc * 64 + ni * 16 + cl, N);
+      }
+    }
+  }
+  // accumulator element (mi, ni, r) with its weight scale applied
+  auto accS = [&](int mi, int ni, int r) __attribute__((always_inline)) {
+    if constexpr (WS) return accv[mi][ni][r] * sv[ni];
+    else return accv[mi][ni][r];
+  };
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
@@ -1355,8 +1395,8 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
           if (col >= P) continue;
           reinterpret_cast<ET*>(a.out)[(size_t)e * a.strideOExpert +
                                        (size_t)m * P + col] =
-              ETr<ET>::fromf(gate_act(accv[mi][2 * j][r], ACT) *
-                             accv[mi][2 * j + 1][r]);
+              ETr<ET>::fromf(gate_act(accS(mi, 2 * j, r), ACT) *
+                             accS(mi, 2 * j + 1, r));
         }
         continue;
       }
@@ -1364,7 +1404,7 @@ __global__ __launch_bounds__(256) void k_group_gemm_bf16(GemmArgs a) {
       for (int ni = 0; ni < 4; ++ni) {
         const int col = n0 + wc * 64 + ni * 16 + cl;
         if (col >= N) continue;
-        float v = accv[mi][ni][r] + bv[ni];
+        float v = accS(mi, ni, r) + bv[ni];
         if constexpr (PHASE == 0) {
           v = (ACT == 0) ? fmaxf(v, 0.0f)
                          : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
@@ -1834,6 +1874,35 @@ __device__ __forceinline__ bool gemm_job_body(
         if (col < N) bv[ni][r] = toF(bptr[col]);
       }
   }
+  // fp8 weights: this job's per-column weight scales, loaded once beside bv
+  // and shaped like it (sv[ni][r] belongs to accv[.][ni][r]). Gated: fragment
+  // 2j is g and 2j+1 is u of P columns pBase + j*16 + r, so the pair takes
+  // s_glu and s_up of the same columns. K-split partials each take the
+  // factor (it distributes over their sum).
+  constexpr bool WS = (BEZ == 1) && (PHASE != 3);
+  float sv[WS ? NF : 1][4];
+  if constexpr (WS) {
+    const float* sp =
+        a.wScale ? a.wScale + (size_t)we * a.wScaleStride : nullptr;
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (GATED) {
+          const int col =
+              (n0 >> 1) + wc * (BN / 8) + cq + (ni >> 1) * 16 + r;
+          sv[ni][r] = wscale_at(
+              sp ? sp + ((ni & 1) ? 0 : a.wScaleGlu) : nullptr, col, N >> 1);
+        } else {
+          sv[ni][r] = wscale_at(sp, nBase + ni * 16 + r, N);
+        }
+      }
+  }
+  // accumulator element (mi, ni, r) with its weight scale applied
+  auto accS = [&](int mi, int ni, int r) __attribute__((always_inline)) {
+    if constexpr (WS) return accv[mi][ni][r] * sv[ni][r];
+    else return accv[mi][ni][r];
+  };
   // per-expert / per-tile output base, hoisted out of the element loops;
   // wide stores need every row base 8-byte (fp32: 16-byte) aligned
   using OT = typename std::conditional<PHASE == 3, float, ET>::type;
@@ -1915,10 +1984,10 @@ __device__ __forceinline__ bool gemm_job_body(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               if constexpr (GATED) {
-                v[r] = gate_act(accv[mi][2 * no][r], act) *
-                       accv[mi][2 * no + 1][r];
+                v[r] = gate_act(accS(mi, 2 * no, r), act) *
+                       accS(mi, 2 * no + 1, r);
               } else {
-                v[r] = accv[mi][no][r] + bv[no][r];
+                v[r] = accS(mi, no, r) + bv[no][r];
                 if constexpr (PHASE == 0)
                   v[r] = (act == 0)
                       ? fmaxf(v[r], 0.0f)
@@ -1991,7 +2060,7 @@ __device__ __forceinline__ bool gemm_job_body(
           float v[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            v[r] = gate_act(accv[mi][2 * j][r], act) * accv[mi][2 * j + 1][r];
+            v[r] = gate_act(accS(mi, 2 * j, r), act) * accS(mi, 2 * j + 1, r);
           storeRow4<SC1>(orow + col0, v, nValid, FULL || vecOK);
         }
         continue;
@@ -2005,7 +2074,7 @@ __device__ __forceinline__ bool gemm_job_body(
         float v[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          v[r] = accv[mi][ni][r] + bv[ni][r];
+          v[r] = accS(mi, ni, r) + bv[ni][r];
           if constexpr (PHASE == 0)
             v[r] = (act == 0)
                 ? fmaxf(v[r], 0.0f)
@@ -2351,6 +2420,15 @@ __device__ __forceinline__ bool mx_gemm_job_body(
       if (col < N) bv[ni] = toF(bptr[col]);
     }
   }
+  // per-column weight scales of this job (1.0f without scales), beside bv
+  float sv[NF];
+  {
+    const float* sp =
+        a.wScale ? a.wScale + (size_t)we * a.wScaleStride : nullptr;
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+      sv[ni] = wscale_at(sp, n0 + wc * (BN / 4) + ni * 16 + cl, N);
+  }
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
@@ -2364,7 +2442,7 @@ __device__ __forceinline__ bool mx_gemm_job_body(
       for (int ni = 0; ni < NF; ++ni) {
         const int col = n0 + wc * (BN / 4) + ni * 16 + cl;
         if (col >= N) continue;
-        float v = accv[mi][ni][r] + bv[ni];
+        float v = accv[mi][ni][r] * sv[ni] + bv[ni];
         if constexpr (PHASE == 0) {
           v = (act == 0) ? fmaxf(v, 0.0f)
                          : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
@@ -2413,7 +2491,7 @@ __device__ __forceinline__ bool mx_gemm_job_body(
           float mx = 0.0f;
 #pragma unroll
           for (int ni = 0; ni < NF; ++ni) {
-            float v = accv[mi][ni][r] + bv[ni];
+            float v = accv[mi][ni][r] * sv[ni] + bv[ni];
             v = (act == 0)
                     ? fmaxf(v, 0.0f)
                     : 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
@@ -2660,8 +2738,18 @@ constexpr int kDecodeFfnMaxSBf16 = 4;
 constexpr int kDecodeFfnMaxSFp16 = 8;
 constexpr int kDecodeFfnMaxSFp8 = 16;
 
-template <typename ET, typename WET, int PHASE, bool GATED>
-__global__ __launch_bounds__(256) void k_decode_ffn(GemmArgs a) {
+// WS (fp8 weights only): a.wScale is set and the epilogue applies the
+// per-output-channel weight scales. A template flag, not a
+// run-time test of the pointer: with the test, a forward WITHOUT scales
+// measured 1.4 us slower than the parent at S = 4, outside the parent's own
+// range. WS = false is the parent's kernel. The ungated fp8 kernels sit at
+// the register count of four waves per SIMD (LDS allows four blocks per CU);
+// the floor keeps the allocator there for their WS siblings, whose epilogue
+// carries one more value. Every other instantiation keeps the default.
+template <typename ET, typename WET, int PHASE, bool GATED, bool WS = false>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu((WS && !GATED) ? 4 : 1)))
+void k_decode_ffn(GemmArgs a) {
   using vec8 = typename ETr<ET>::vec8;
   constexpr int BEZ = (int)sizeof(WET);
   constexpr int KPL = 16 / BEZ;               // K elements per 16-B load
@@ -2700,6 +2788,17 @@ __global__ __launch_bounds__(256) void k_decode_ffn(GemmArgs a) {
   Bw[0] = reinterpret_cast<const WET*>(a.B) + (size_t)we * a.strideBExpert +
           (size_t)(n0 + rl) * K + q * KPL;
   if constexpr (GATED) Bw[1] = Bw[0] + a.gluOffset;
+  // WS: the weight scale(s) of this block's column, loaded once per block by
+  // the wave that runs the epilogue (s0: the one matrix / u, s1: g)
+  float s0 = 1.0f, s1 = 1.0f;
+  if constexpr (WS) {
+    static_assert(BEZ == 1, "weight scales belong to fp8 weights");
+    if (wave == 0) {
+      const float* sp = a.wScale + (size_t)we * a.wScaleStride + n0 + rl;
+      s0 = sp[0];
+      if constexpr (GATED) s1 = sp[a.wScaleGlu];
+    }
+  }
 
   for (int mg0 = 0; mg0 < (int)routed; mg0 += kDecRows) {
     const int rp = min((int)routed - mg0, kDecRows);
@@ -2831,6 +2930,17 @@ __global__ __launch_bounds__(256) void k_decode_ffn(GemmArgs a) {
       float bv = 0.0f;
       if (a.bias)
         bv = toF(reinterpret_cast<const ET*>(a.bias)[(size_t)we * N + col]);
+      // WS: the reduced sums take the column's weight scale(s) in place
+      // (acc[0]: the one matrix / u, acc[1]: g)
+      if constexpr (WS) {
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            acc[0][f][r] *= s0;
+            if constexpr (GATED) acc[1][f][r] *= s1;
+          }
+      }
       const bool multi = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
       const bool scaled =
           (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
@@ -3763,8 +3873,8 @@ struct State {
   unsigned long long seq = 0;
   // transparent hipGraph cache for repeated-pointer forwards
   hipGraphExec_t graphExec = nullptr;
-  void* graphKey[8] = {};
-  void* lastKey[8] = {};
+  void* graphKey[10] = {};
+  void* lastKey[10] = {};
   bool graphValid = false;
   void* xM = nullptr;        // [nLx_alloc, pEC, P] Element
   uint8_t* x8 = nullptr;     // dtype 5: quantized activations [S, H]
@@ -3788,8 +3898,28 @@ struct State {
   fm_router_config router{0, 1, 1, 1, 0, 1.0f, nullptr};
   bool routerRV = false;    // any non-default field: the RV gate kernels
   uint32_t routerGen = 0;   // bumped per fm_set_router: part of the graph key
+  // per-output-channel fp32 scales of the fp8 expert weights
+  // (fm_set_weight_scales): borrowed device tensor
+  // [nLx + nSh, P + H (+ P gated)], record = [s_up | s_dn | s_glu]
+  const float* wScale = nullptr;
+  int wScaleGran = 0;        // 0 none, 1 per output channel
+  uint32_t wScaleGen = 0;    // bumped per set call: part of the graph key
 };
 State g;
+
+// Point a launch at the weight scales of its phase (0 up, 1 down): the
+// record of weight expert `firstExpert`, offset to the phase's vector. The
+// kernels add we * stride; entry points that pre-select one expert pass its
+// id here and a launch whose z-slices all read that record (stride 0).
+static void setWeightScaleArgs(GemmArgs& a, int phase, int firstExpert,
+                               bool strided) {
+  const long long SC = (long long)g.P + g.H + (g.gated ? g.P : 0);
+  a.wScale = g.wScale ? g.wScale + (size_t)firstExpert * SC +
+                            (phase == 0 ? 0 : g.P)
+                      : nullptr;
+  a.wScaleStride = strided ? SC : 0;
+  a.wScaleGlu = g.P + g.H;  // s_up -> s_glu inside a record (gated up phase)
+}
 
 // kernel-side view of g.router
 static RouterP routerParams() {
@@ -4336,6 +4466,8 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   if (!cfg) { setErr("null config"); return FM_ERR_STATE; }
   g.router = State{}.router;  // a fresh config starts from the default router
   g.routerRV = false;
+  g.wScale = nullptr;  // and without weight scales
+  g.wScaleGran = 0;
   g.cfg = *cfg;
   g.rank = rank;
   g.world = world_size;
@@ -4681,6 +4813,42 @@ int fm_set_router(const fm_router_config* r) {
   g.router = c;
   g.routerRV = rv;
   ++g.routerGen;  // never replay a forward captured under another router
+  return FM_OK;
+}
+
+int fm_set_weight_scales(const float* scales, int32_t granularity) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (granularity == 2) {
+    setErr("weight scale granularity 2 (128x128 blocks) is reserved: block "
+           "scales vary along K and need in-loop handling (DESIGN.md 5l)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (granularity != 0 && granularity != 1) {
+    snprintf(g_err, sizeof(g_err),
+             "weight scale granularity must be 0 (none) or 1 (per output "
+             "channel); got %d", (int)granularity);
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (granularity == 1 && g.cfg.dtype != 4 && g.cfg.dtype != 5) {
+    snprintf(g_err, sizeof(g_err),
+             "weight scales need fp8 expert weights: torch_dtype must be 4 or "
+             "5, the config has torch_dtype %d", (int)g.cfg.dtype);
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (granularity == 1 && !scales) {
+    setErr("null weight scales with granularity 1");
+    return FM_ERR_STATE;
+  }
+  g.wScale = granularity == 1 ? scales : nullptr;
+  g.wScaleGran = granularity;
+  ++g.wScaleGen;  // never replay a forward captured under other scales
+  return FM_OK;
+}
+
+int fm_get_weight_scales(const float** scales, int32_t* granularity) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (scales) *scales = g.wScale;
+  if (granularity) *granularity = g.wScaleGran;
   return FM_OK;
 }
 
@@ -5058,21 +5226,22 @@ static int launch_decode_ffn(hipStream_t st, int phase, const GemmArgs& a,
   GemmArgs aa = a;
   aa.gluOffset = gated ? 2LL * a.N * a.K : 0;  // Wup (slot 0) -> Wglu (slot 2)
   const dim3 grid(a.N / 16, nZ), block(256);
-#define DEC_ET(ET, WET)                                                       \
+#define DEC_ET(ET, WET, WS)                                                   \
   do {                                                                        \
     if (phase == 1)                                                           \
-      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 1, false>), grid, block, 0,   \
-                         st, aa);                                             \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 1, false, WS>), grid, block,  \
+                         0, st, aa);                                          \
     else if (gated)                                                           \
-      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, true>), grid, block, 0,    \
-                         st, aa);                                             \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, true, WS>), grid, block,   \
+                         0, st, aa);                                          \
     else                                                                      \
-      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, false>), grid, block, 0,   \
-                         st, aa);                                             \
+      hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, false, WS>), grid, block,  \
+                         0, st, aa);                                          \
   } while (0)
-  if (g.cfg.dtype == 3) DEC_ET(fp16, fp16);
-  else if (g.cfg.dtype == 4) DEC_ET(bf16, fp8e4m3);
-  else DEC_ET(bf16, bf16);
+  if (g.cfg.dtype == 3) DEC_ET(fp16, fp16, false);
+  else if (g.cfg.dtype == 4 && aa.wScale) DEC_ET(bf16, fp8e4m3, true);
+  else if (g.cfg.dtype == 4) DEC_ET(bf16, fp8e4m3, false);
+  else DEC_ET(bf16, bf16, false);
 #undef DEC_ET
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
@@ -5163,8 +5332,11 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // (nor does a non-default router: k_moe_fused routes with the legacy
   // route_tile_core)
   // (nor does a decode-sized forward, S < 128: no ragged tile there)
+  // (nor does a forward with weight scales attached: k_moe_fused is not
+  // taught about them, its GemmArgs carry none)
   if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
-      g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV) {
+      g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV &&
+      !g.wScale) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -5211,6 +5383,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   up.EC = g.EC; up.pEC = g.pEC; up.PX = g.PX;
   up.topk = g.cfg.expert_top_k; up.act = g.cfg.hidden_act;
   up.expertOffset = 0; up.nRows = 0; up.H = g.H;
+  setWeightScaleArgs(up, 0, 0, true);
   // shared experts ride both launches as nV extra z-slices (static routing
   // tail, fm_initialize); null map / zero counts when there are none
   const int nZ = g.E + g.nV;
@@ -5253,6 +5426,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   dn.moe_out = moe_out;
   dn.strideAExpert = (long long)g.pEC * g.P;
   dn.K = g.P; dn.N = g.H;
+  setWeightScaleArgs(dn, 1, 0, true);
   rc = decode ? launch_decode_ffn(st, 1, dn, nZ)
               : launch_group_gemm(st, 1, dn, g.pEC, nZ);
   if (rc != FM_OK) return rc;
@@ -5283,14 +5457,16 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
   // capture the 6-launch sequence once and replay it (saves the
   // per-launch host+boundary overhead; falls back to eager whenever any
   // pointer changes or capture is unavailable).
-  void* key[8] = {const_cast<void*>(x), const_cast<void*>(gate_w),
+  void* key[10] = {const_cast<void*>(x), const_cast<void*>(gate_w),
                   const_cast<void*>(expert_w), const_cast<void*>(b_up),
                   const_cast<void*>(b_dn), gate_out, moe_out,
                   reinterpret_cast<void*>(static_cast<uintptr_t>(
                       (uint64_t)g.routerGen << 40 |
                       (uint64_t)(decodeFfnMode() + 1) << 38 |
                       (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
-                      (fusedEnabled() ? 1 : 0)))};
+                      (fusedEnabled() ? 1 : 0))),
+                  const_cast<float*>(g.wScale),
+                  reinterpret_cast<void*>(static_cast<uintptr_t>(g.wScaleGen))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;
     g.graphValid = false;  // replay failed: rebuild next time
@@ -5437,6 +5613,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   up.K = g.H; up.N = g.P; up.EC = 0; up.pEC = 0; up.PX = g.PX;
   up.topk = 1; up.act = g.cfg.hidden_act; up.expertOffset = 0;
   up.nRows = (int)n_rows; up.H = g.H;
+  setWeightScaleArgs(up, 0, local_e, false);  // like B: pre-offset, stride 0
   int rc = launch_group_gemm(st, 0, up, (int)n_rows, 1);
   if (rc != FM_OK) return rc;
   // note: PHASE 0 with tokenIds==nullptr writes out[e=0 stride 0] = xM rows
@@ -5447,6 +5624,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   dn.bias = b_dn;
   dn.out = out_rows;
   dn.K = g.P; dn.N = g.H;
+  setWeightScaleArgs(dn, 1, local_e, false);
   return launch_group_gemm(st, 2, dn, (int)n_rows, 1);
 }
 
@@ -5703,6 +5881,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   up.H = g.H;
   up.splitK = 1;
   up.segExpert = reinterpret_cast<const int32_t*>(seg_expert_dev);
+  setWeightScaleArgs(up, 0, 0, true);  // indexed by the mapped weight expert
   const bool mxEpiQuant =
       (g.cfg.dtype == 5) && mxWideN(g.EC, g.P, n_segs);
   if (mxEpiQuant) {
@@ -5727,6 +5906,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   dn.strideOExpert = (long long)g.EC * g.H;
   dn.K = g.P;
   dn.N = g.H;
+  setWeightScaleArgs(dn, 1, 0, true);
   return launch_group_gemm(st, 2, dn, g.EC, n_segs);
 }
 

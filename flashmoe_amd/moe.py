@@ -22,6 +22,7 @@ _state = {
     "gate_out": None,  # persistent [S, PX] buffer (internal, like the
     # reference's flat-buffer gate output, python_bindings.cu:70-74)
     "score_bias": None,  # the fp32 [E] tensor fm_set_router borrows
+    "weight_scales": None,  # the fp32 tensor fm_set_weight_scales borrows
 }
 
 
@@ -69,7 +70,7 @@ def initialize(config_path: str | None = None, rank: int | None = None,
     )
     _ext.check(lib.fm_initialize(ctypes.byref(c), rank, world_size), "fm_initialize")
     _state.update(initialized=True, cfg=cfg, rank=rank, world=world_size,
-                  score_bias=None)
+                  score_bias=None, weight_scales=None)
     if not router_is_default(cfg):
         try:
             _apply_router()
@@ -90,7 +91,8 @@ def finalize():
     if not _state["initialized"]:
         raise RuntimeError("finalize() before initialize()")
     _ext.check(_ext.load().fm_finalize(), "fm_finalize")
-    _state.update(initialized=False, cfg=None, gate_out=None, score_bias=None)
+    _state.update(initialized=False, cfg=None, gate_out=None, score_bias=None,
+                  weight_scales=None)
     _state.pop("p2p", None)        # heap freed by fm_finalize
     _state.pop("ep_buffers", None)
     # a P2P setup failure is scoped to one initialize/finalize cycle
@@ -157,6 +159,124 @@ def get_router() -> dict:
             "group_score": c.group_score,
             "routed_scaling_factor": float(c.routed_scaling_factor),
             "score_bias": bias}
+
+
+def _weight_scale_shape():
+    """(records, SC) of the weight-scale tensor for the initialized config:
+    one record [s_up (P) | s_dn (H) | s_glu (P, gated only)] per local routed
+    expert, then one per shared expert."""
+    cfg = _state["cfg"]
+    P, H = cfg["intermediate_size"], cfg["hidden_size"]
+    n = _ext.load().fm_get_num_local_experts() + num_shared(cfg)
+    return n, P + H + (P if expert_mats(cfg["hidden_act"]) == 3 else 0)
+
+
+def set_weight_scales(scales):
+    """Attach (or, with None, detach) per-output-channel fp32 scales of the
+    fp8 expert weights (torch_dtype 4 and 5): W_eff[r, :] = W_fp8[r, :] * s[r],
+    applied to the fp32 accumulators ahead of bias and activation (DESIGN.md
+    par.5l). `scales` is a contiguous float32 CUDA tensor [nLx + nSh, SC] as
+    built by pack_weight_scales. The tensor is borrowed by the library and
+    kept alive here; its contents may be rewritten in place between
+    forwards."""
+    import torch
+
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    lib = _ext.load()
+    if scales is None:
+        _ext.check(lib.fm_set_weight_scales(None, 0), "fm_set_weight_scales")
+        _state["weight_scales"] = None
+        return
+    dt = _state["cfg"]["torch_dtype"]
+    if dt not in (4, 5):
+        raise ValueError(
+            f"weight scales need fp8 expert weights (torch_dtype 4 or 5); the "
+            f"initialized config has torch_dtype {dt}")
+    want = _weight_scale_shape()
+    if not isinstance(scales, torch.Tensor) or not scales.is_cuda:
+        raise ValueError(
+            f"weight scales must be a CUDA float32 tensor of shape "
+            f"[nLx + nSh, SC] = {list(want)}")
+    if scales.dtype != torch.float32 or tuple(scales.shape) != want or \
+            not scales.is_contiguous():
+        raise ValueError(
+            f"weight scales must be a contiguous float32 tensor of shape "
+            f"[nLx + nSh, SC] = {list(want)}; got {scales.dtype} "
+            f"{list(scales.shape)}")
+    _ext.check(lib.fm_set_weight_scales(ctypes.c_void_p(scales.data_ptr()), 1),
+               "fm_set_weight_scales")
+    _state["weight_scales"] = scales
+
+
+def get_weight_scales():
+    """The attached weight-scale tensor, or None, as the library reports it
+    (fm_get_weight_scales). Scales attached through the raw C-ABI are not a
+    tensor this module holds: RuntimeError."""
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    ptr, gran = ctypes.c_void_p(), ctypes.c_int32()
+    _ext.check(_ext.load().fm_get_weight_scales(ctypes.byref(ptr),
+                                                ctypes.byref(gran)),
+               "fm_get_weight_scales")
+    if gran.value == 0:
+        return None
+    t = _state["weight_scales"]
+    if t is None or t.data_ptr() != (ptr.value or 0):
+        raise RuntimeError(
+            f"weight scales at {ptr.value or 0:#x} (granularity {gran.value}) "
+            f"were attached through fm_set_weight_scales directly, not through "
+            f"set_weight_scales: there is no tensor to return")
+    return t
+
+
+def pack_weight_scales(up, down, glu=None):
+    """Build the [nE, SC] weight-scale tensor from per-matrix scales: `up`
+    [nE, P] (rows of Wup), `down` [nE, H] (rows of the down buffer used as
+    [H, P]) and, for gated experts, `glu` [nE, P]. nE counts the shared
+    experts, which come last. Every size-1 dimension broadcasts, and a 0-dim
+    or 1-D [nE] tensor is a per-tensor scale: [nE], [nE, 1], [1] and 0-dim all
+    spread over the channels (and the last two over the experts). nE, P and H
+    come from the dimensions larger than 1, else from the initialized config.
+    Returns a contiguous float32 tensor on the device of the first argument
+    that has channels, with records [s_up | s_dn | s_glu]."""
+    import torch
+
+    named = [("up", up), ("down", down)] + ([("glu", glu)] if glu is not None
+                                            else [])
+    parts = []
+    for name, t in named:
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.dim() > 2:
+            raise ValueError(f"{name} scales must have at most 2 dimensions; "
+                             f"got {list(t.shape)}")
+        # 0-dim -> [1, 1]; [n] -> [n, 1]: one value per expert
+        parts.append(t.reshape(t.size(0) if t.dim() else 1, -1))
+
+    def agreed(what, sizes, fallback):
+        """The one size > 1 among `sizes`; `fallback` when all broadcast."""
+        big = sorted({n for n in sizes if n != 1})
+        if len(big) > 1:
+            raise ValueError(f"pack_weight_scales: the arguments disagree on "
+                             f"{what}: {big}")
+        if big:
+            return big[0]
+        if fallback is None:
+            raise ValueError(
+                f"pack_weight_scales cannot infer {what} from broadcast "
+                f"(size-1) arguments alone: pass it in a tensor's shape, or "
+                f"call after initialize()")
+        return fallback
+
+    cfg = _state["cfg"]
+    nE = agreed("the expert count nE", [t.size(0) for t in parts],
+                _weight_scale_shape()[0] if cfg else 1)
+    P = agreed("P", [t.size(1) for t in parts[0::2]],
+               cfg["intermediate_size"] if cfg else None)
+    H = agreed("H", [parts[1].size(1)], cfg["hidden_size"] if cfg else None)
+    dev = next((t.device for t in parts if t.size(1) != 1), parts[0].device)
+    cols = [t.to(dev).expand(nE, w) for t, w in zip(parts, (P, H, P))]
+    return torch.cat(cols, dim=1).contiguous()
 
 
 def get_compiled_config() -> dict:
@@ -263,16 +383,20 @@ def _validate_forward_args(input, gate_weights, expert_weights):
     return S, H, E, P, nLx
 
 
-def moe_forward(input, gate_weights, expert_weights):
+def moe_forward(input, gate_weights, expert_weights, weight_scales=None):
     """Mirror of _C.moe_forward (python_bindings.cu:17-151): one DMoE
     forward on this rank's tokens. Single-rank path; world>1 uses the EP
     pipeline in ep.py (same result per rank). With
     num_shared_experts = nSh > 0 expert_weights is [nLx + nSh, mats, P, H]
     (shared slabs last) and every token also receives the unscaled sum of
-    the shared FFNs."""
+    the shared FFNs. weight_scales (torch_dtype 4 / 5): a
+    tensor as for set_weight_scales; one that is not the attached tensor is
+    attached first, None leaves the attachment as it is."""
     import torch
 
     S, H, E, P, nLx = _validate_forward_args(input, gate_weights, expert_weights)
+    if weight_scales is not None and weight_scales is not _state["weight_scales"]:
+        set_weight_scales(weight_scales)
     if _state["world"] != 1:
         from . import ep
 

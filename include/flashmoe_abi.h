@@ -38,7 +38,8 @@ extern "C" {
  * runtime-quantized fp8 activations (per-64-element E8M0 block scales)
  * on the CDNA4 scaled MFMA; weights are passed exactly as for dtype 4,
  * activation quantization is internal. dtype 5 requires H, P multiples
- * of 128.
+ * of 128. For dtype 4 and 5 the weight scale is 1.0 unless scales are
+ * attached with fm_set_weight_scales (per output channel, below).
  *
  * hidden_act: 0 relu, 1 exact-erf gelu: z = act(x.Wup^T + b_up).Wdn^T + b_dn
  * with expert weights [nLx, 2, P, H]. 2 SwiGLU (silu(v) = v / (1 + exp(-v)))
@@ -170,6 +171,35 @@ typedef struct fm_router_config {
 } fm_router_config;
 int fm_set_router(const fm_router_config* r); /* NULL = defaults */
 int fm_get_router(fm_router_config* out);
+
+/* Weight scales of the fp8 expert weights (dtype 4 and 5; DESIGN.md
+ * par.5l). Without them the weights are raw e4m3 with scale 1.0. With
+ * granularity 1 every weight matrix row (output channel) r has an fp32 scale:
+ *   W_eff[r, :] = float(W_fp8[r, :]) * s[r]
+ * applied to the fp32 accumulator ahead of bias and activation:
+ *   up, ungated  act(acc * s_up[p] + b_up[p])
+ *   up, gated    act(g * s_glu[p]) * (u * s_up[p])
+ *   down         acc * s_dn[h] + b_dn[h], then the combine as before
+ * (dtype 5: the same; the in-epilogue activation quantisation sees the
+ * scaled values). A per-tensor scale is the same value in every channel.
+ * scales: device fp32, contiguous [nLx + nSh, SC], SC = P + H (+ P when
+ * gated); an expert's record is [s_up (P) | s_dn (H) | s_glu (P)] - the slab
+ * order - and the shared experts' records trail the routed ones. Every value
+ * must be finite; the contents are not checked.
+ * granularity: 0 none (scales ignored, may be NULL), 1 per output channel,
+ * 2 reserved for 128x128 blocks -> FM_ERR_UNSUPPORTED.
+ * Valid after fm_initialize; fm_initialize and fm_finalize reset to none.
+ * The tensor is BORROWED until the next fm_set_weight_scales / fm_finalize;
+ * the caller may rewrite its contents in place between forwards. A set call
+ * invalidates the captured forward graph. Read by fm_moe_forward,
+ * fm_moe_forward_phased, fm_expert_ffn, fm_expert_ffn_segments and
+ * fm_expert_ffn_grouped (indexed by weight expert, like the bias slabs). A
+ * forward with scales attached always runs the multi-kernel path
+ * (fm_last_forward_fused() reports 0).
+ * FM_ERR_UNSUPPORTED (the message names the cause): granularity 1 with a
+ * torch_dtype other than 4 or 5; granularity 2. */
+int fm_set_weight_scales(const float* scales, int32_t granularity);
+int fm_get_weight_scales(const float** scales, int32_t* granularity);
 
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */

@@ -2,6 +2,7 @@
 
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
                                    [--router qwen|v2|v3|sigmoid]
+                                   [--weight-scales]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -25,7 +26,9 @@ weight_bytes, the bytes of all weight slabs of the routed experts with rows
 counted once, and floor_us = weight_bytes /
 6.3 TB/s, a bytes bound. --decode-ab R (S < 128) times R
 runs of `steps` forwards under FM_DECODE_FFN=1 and R under =0, alternated,
-and reports every run.
+and reports every run. --weight-scales (dtype 4 and 5 only, DESIGN.md
+par.5l) attaches a random per-output-channel weight-scale tensor,
+exp2(U(-2, 1)) per channel.
 """
 import ctypes
 import json
@@ -71,6 +74,9 @@ if "--router" in argv:
 mini_batch_form = "--mini-batch" in argv
 if mini_batch_form:
     argv.remove("--mini-batch")
+weight_scales = "--weight-scales" in argv
+if weight_scales:
+    argv.remove("--weight-scales")
 ab_runs = 0
 if "--decode-ab" in argv:
     i = argv.index("--decode-ab")
@@ -88,6 +94,9 @@ dtype_code = args[6] if len(args) > 6 else 2
 
 from flashmoe_amd.config import expert_mats, torch_dtype_of, weight_dtype_of
 
+if weight_scales and dtype_code not in (4, 5):
+    sys.exit("--weight-scales needs fp8 expert weights: dtype 4 or 5")
+
 adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
 x_first = torch.randn(1, s_list[0], H, dtype=adt, device="cuda")
@@ -100,6 +109,14 @@ if router in ("v3", "sigmoid"):
 ew_all = torch.randn(E + n_shared + n_compose, expert_mats(hidden_act), P, H,
                      dtype=torch.float32, device="cuda").to(wdt)
 ew = ew_all[:E + n_shared]  # what moe_forward sees (a leading slice)
+w_scales = None
+if weight_scales:
+    # a generator of its own: the inputs drawn later stay those of a run
+    # without the flag
+    w_scales = torch.exp2(3.0 * torch.rand(
+        E + n_shared, P + H + (P if expert_mats(hidden_act) == 3 else 0),
+        dtype=torch.float32, device="cuda",
+        generator=torch.Generator(device="cuda").manual_seed(48)) - 2.0)
 lib = _ext.load()
 HBM_ACHIEVABLE = 6.3e12  # bytes/s
 
@@ -123,6 +140,8 @@ def measure(S):
     os.unlink(f.name)
     if score_bias is not None:
         moe.set_score_bias(score_bias)
+    if w_scales is not None:
+        moe.set_weight_scales(w_scales)
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
     x = x.view(cfg["mini_batch"], cfg["sequence_len"], H)
@@ -204,7 +223,8 @@ def measure(S):
                      f"dtype{dtype_code} act{hidden_act} CF=1 drop"
                      + (f" shared={n_shared}" if n_shared else "")
                      + (f" compose={n_compose}" if n_compose else "")
-                     + (f" router={router}" if router else "")),
+                     + (f" router={router}" if router else "")
+                     + (" weight-scales" if weight_scales else "")),
         "us_per_fwd": round(dt * 1e6, 1),
         "tokens_per_s": round(S / dt),
         "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
