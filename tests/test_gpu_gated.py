@@ -293,8 +293,10 @@ def run_child(env_extra, runs=1, want_classic=False, **cfg):
     assert "CHILD OK" in r.stdout
 
 
-# S=512, E=2, top-2, CF=2: pEC = 1024 rows per expert, about half routed,
-# so every tile mode sees partly filled and wholly empty M tiles. P=320:
+# S=512, E=2, top-2, CF=2: every token selects both experts, so each has
+# exactly 512 of its pEC = 1024 rows routed (pinned in test_loads_cpu.py):
+# every tile mode sees full M tiles followed by wholly empty ones, never a
+# partly filled one - test_gpu_loads.py has those. P=320:
 # the effective N = 640 is two full 256-wide tiles plus a half tile (five
 # 128-wide ones), so the last tile's gate AND up halves both run past
 # P - the per-half clamp and the ragged epilogue.

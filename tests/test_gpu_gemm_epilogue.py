@@ -104,9 +104,11 @@ def run_child(env_extra, runs=1, bias=False, **cfg):
     assert "CHILD OK" in r.stdout
 
 
-# S=512, E=2, top-2, CF=2: pEC = 1024 rows per expert of which ~512 are
-# routed, so every forced tile mode sees a partly filled M tile and wholly
-# empty M tiles; H=192 / P=320 are ragged against 128 and 256, so the last
+# S=512, E=2, top-2, CF=2: every token selects both experts, so each has
+# exactly 512 of its pEC = 1024 rows routed (pinned in test_loads_cpu.py) -
+# full M tiles followed by wholly empty ones in every forced tile mode, never
+# a partly filled one: test_gpu_loads.py places the row counts on the tile
+# edges. H=192 / P=320 are ragged against 128 and 256, so the last
 # N tile has column groups that lie past N (and the B-row clamp) in both
 # the up (PHASE 0) and the down (PHASE 1) GEMM.
 RAGGED = dict(sequence_len=512, num_experts=2, expert_top_k=2,

@@ -8,7 +8,9 @@ order in an expert's token list comes from atomicAdd, so when an expert
 OVERFLOWS capacity the kept-token SET is schedule-dependent — in the
 reference too. Exact-output tests therefore use either one 128-token tile
 (deterministic) or capacity that cannot overflow; full-size runs check
-invariants and a capacity-safe configuration.
+invariants and a capacity-safe configuration. Values under multi-tile
+overflow are checked in test_gpu_loads.py, against a reference conditioned
+on the kernel's own kept set.
 """
 import ctypes
 import json
@@ -576,171 +578,6 @@ def test_mx_mfma_layout_probe():
     assert torch.allclose(got, want, rtol=1e-3, atol=1e-2), (
         f"MX MFMA layout mismatch: max err {(got-want).abs().max().item()}"
     )
-
-
-def test_single_tile_gelu(fresh_moe):
-    cfg, path = make_cfg(hidden_act=1)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-def test_single_tile_top4(fresh_moe):
-    cfg, path = make_cfg(expert_top_k=4, num_experts=16)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-def test_mini_batch_2(fresh_moe):
-    """mini_batch > 1: input [b, s, H] with S = b*s (python_bindings.cu
-    validates batch*seq == compiled S; tokens are row-major across the
-    batch)."""
-    cfg, path = make_cfg(mini_batch=2, sequence_len=128, capacity_factor=2)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert out.shape[0] == 256
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-@pytest.mark.parametrize("k", [3, 5, 7])
-def test_single_tile_odd_topk(fresh_moe, k):
-    """Non-power-of-two top-k (the reference schema allows any k >= 1)."""
-    cfg, path = make_cfg(expert_top_k=k, num_experts=16, capacity_factor=2)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-@pytest.mark.parametrize("E,k", [(192, 2), (256, 4)])
-def test_many_experts_gate(fresh_moe, E, k):
-    """E > 128 (config-5 shape): the expert-chunked gate logits kernel
-    and >=192-way top-k routing."""
-    # single 128-token tile: routing deterministic even if an expert
-    # overflows its tiny capacity (EC = ceil(128/E)*CF*k)
-    cfg, path = make_cfg(num_experts=E, expert_top_k=k, sequence_len=128,
-                         capacity_factor=2)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert_values(gate_out, ref["gate_out"], "bf16", "gate_out")
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-def test_multi_tile_no_overflow_bf16(fresh_moe):
-    """Multi-tile S with capacity_factor 2 (overflow-free): exact output
-    parity across the nondeterministic tile order."""
-    cfg, path = make_cfg(sequence_len=1024, capacity_factor=2,
-                         hidden_size=256, intermediate_size=512)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    S, E = 1024, 8
-    EC = (S // E) * 2 * 2  # ceil(S/E)*CF*k = 512
-    counts, _, _ = routing_from_lib(E, EC)
-    assert counts.astype(np.int64).sum() == ref["eC"].sum() == S * 2
-    assert np.array_equal(np.sort(counts.astype(np.int64)), np.sort(ref["eC"]))
-    assert_values(gate_out, ref["gate_out"], "bf16", "gate_out")
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-def test_training_aux_loss(fresh_moe):
-    """is_training=1: gML (mean gate prob) and gMeC (routed fraction)
-    accumulators vs the oracle (gate.cuh:273-299,763-773)."""
-    from oracle.moe_oracle import gate_aux_loss
-    import flashmoe_amd._ext as _ext
-
-    cfg, path = make_cfg(is_training=1, sequence_len=512)
-    out, gate_out, ref, ocfg = run_pair(fresh_moe, cfg, path)
-    E = cfg["num_experts"]
-    lib = _ext.load()
-    gML = np.zeros(E, dtype=np.float32)
-    gMeC = np.zeros(E, dtype=np.float32)
-    _ext.check(lib.fm_read_aux_loss(
-        None, ctypes.c_void_p(gML.ctypes.data),
-        ctypes.c_void_p(gMeC.ctypes.data)), "aux_loss")
-    # oracle reference on the same inputs
-    S, H = 512, cfg["hidden_size"]
-    g = torch.Generator(device="cpu").manual_seed(47)
-    x = torch.randn(1, 512, H, generator=g).to(torch.bfloat16)
-    gw = torch.randn(H, E, generator=g).to(torch.bfloat16)
-    want_gML, want_gMeC = gate_aux_loss(
-        x.view(S, H).float().numpy(),
-        gw.float().numpy().reshape(-1).reshape(E, H), ocfg)
-    np.testing.assert_allclose(gML, want_gML, rtol=1e-2, atol=1e-4)
-    np.testing.assert_allclose(gMeC, want_gMeC, rtol=1e-5, atol=1e-6)
-
-
-def test_full_bench_size_exact_no_overflow(fresh_moe):
-    """Exact value parity at the FULL bench size (S=4096, H=1024, P=4096,
-    E=8, k=2) with capacity_factor 2, where no expert can overflow -> the
-    kept set is deterministic and the whole [4096, 1024] output must meet
-    the tolerance bar vs the oracle (the strongest full-size guarantee the
-    routing nondeterminism permits)."""
-    cfg, path = make_cfg(sequence_len=4096, hidden_size=1024,
-                         intermediate_size=4096, capacity_factor=2)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    assert int(ref["eC"].sum()) == 4096 * 2  # nothing dropped
-    assert_values(gate_out, ref["gate_out"], "bf16", "gate_out")
-    assert_values(out, ref["moe_out"], "bf16", "moe_out")
-
-
-def test_bench_config_invariants(fresh_moe):
-    """BASELINE config 2 at full size (S=4096, H=1024, P=4096, E=8, k=2,
-    CF=1): size-independent properties + routing counts vs oracle
-    (kept SETS under overflow are schedule-dependent, as in the
-    reference — checked via counts, probs, and finiteness)."""
-    cfg, path = make_cfg(sequence_len=4096, hidden_size=1024,
-                         intermediate_size=4096)
-    out, gate_out, ref, _ = run_pair(fresh_moe, cfg, path)
-    S, E, EC = 4096, 8, 1024
-    counts, tok, ps = routing_from_lib(E, EC)
-    # raw eC is deterministic -> clipped counts match the oracle's
-    assert np.array_equal(counts.astype(np.int64), np.minimum(ref["eC"], EC))
-    # gate probabilities are schedule-independent
-    assert_values(gate_out, ref["gate_out"], "bf16", "gate_out")
-    g = gate_out.float().cpu().numpy()
-    np.testing.assert_allclose(g[:, :E].sum(1), 1.0, atol=2e-2)
-    assert np.isfinite(out.float().cpu().numpy()).all()
-    # each kernel-kept (token, expert) slot carries the oracle's mCw
-    mcw = ref["mCw"]
-    for e in range(E):
-        sl = slice(0, counts[e])
-        np.testing.assert_allclose(ps[e, sl], mcw[tok[e, sl]], rtol=2e-2)
-
-
-def test_device_task_queue_probe():
-    """Round-2 groundwork: the seqlock MPMC device task ring (subscriber/
-    scheduler semantics, os/subscriber.cuh:333-451 / scheduler.cuh:296-441)
-    delivers every task exactly once across producer/consumer blocks,
-    including ring wrap-around (nTasks >> ring size)."""
-    import __graft_entry__  # noqa: F401
-    import flashmoe_amd._ext as _ext
-
-    lib = _ext.load()
-    n_tasks, ring, blocks = 200_000, 1024, 64
-    out = [ctypes.c_uint32() for _ in range(3)]
-    _ext.check(lib.fm_debug_taskq(
-        None, ring, ctypes.c_longlong(n_tasks), blocks,
-        *[ctypes.byref(o) for o in out]), "fm_debug_taskq")
-    got_sum, consumed, errors = [int(o.value) for o in out]
-    want_sum = sum((s * 2654435761) & 0xFFFFFFFF for s in range(n_tasks)) \
-        & 0xFFFFFFFF
-    assert errors == 0
-    assert consumed == n_tasks
-    assert got_sum == want_sum
-
-
-def test_error_behaviour(fresh_moe):
-    """Shape/device validation mirrors the reference's TORCH_CHECKs
-    (python_bindings.cu:22-70)."""
-    cfg, path = make_cfg()
-    fresh_moe.initialize(path, rank=0, world_size=1)
-    H, E, P = 128, 8, 256
-    x = torch.randn(1, 128, H, dtype=torch.bfloat16, device="cuda")
-    gw = torch.randn(H, E, dtype=torch.bfloat16, device="cuda")
-    ew = torch.randn(E, 2, P, H, dtype=torch.bfloat16, device="cuda")
-    with pytest.raises(ValueError, match="batch\\*seq"):
-        fresh_moe.moe_forward(x[:, :64], gw, ew)
-    with pytest.raises(ValueError, match="Gate weights"):
-        fresh_moe.moe_forward(x, gw.T.contiguous(), ew)
-    xx = torch.randn(1, 128, 2 * H, dtype=torch.bfloat16, device="cuda")[..., ::2]
-    with pytest.raises(ValueError, match="contiguous"):
-        fresh_moe.moe_forward(xx, gw, ew)
-    with pytest.raises(ValueError, match="Expert count"):
-        fresh_moe.moe_forward(x, gw, ew[:4])
 
 
 def test_single_tile_mx_fp8(fresh_moe):

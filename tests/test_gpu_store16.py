@@ -38,7 +38,8 @@ CLASSIC = {"FM_FUSED": "0"}
 
 @pytest.mark.parametrize("mode", [0, 1, 3, 4])
 def test_store16_forced_tile_modes_bf16(mode):
-    """RAGGED: partly filled and empty M tiles, a ragged last N tile (the
+    """RAGGED: 512 rows per expert - full M tiles followed by empty ones
+    (partly filled ones: test_gpu_loads.py) - a ragged last N tile (the
     per-lane column check of the 16-byte path), 16-byte-aligned rows
     (H=192, P=320 are multiples of 8). PHASE 0 plain and PHASE 1 slots."""
     run_child({"FM_FORCE_MODE": str(mode), **CLASSIC}, **RAGGED)

@@ -543,9 +543,11 @@ def run_child(env_extra, cfgs, runs=1, fused=False):
     assert "CHILD OK" in r.stdout
 
 
-# test_gpu_gated's forced-mode shape: S=512, E=2, top-2, CF=2 (pEC = 1024 rows
-# per expert, about half routed: partly filled and empty M tiles in every tile
-# mode), H=192 / P=320 ragged against the 128- and 256-wide tiles. relu and
+# test_gpu_gated's forced-mode shape: S=512, E=2, top-2, CF=2 (every token
+# selects both experts: exactly 512 of the pEC = 1024 rows per expert routed,
+# full M tiles followed by empty ones in every tile mode; partly filled tiles
+# are in test_gpu_loads.py), H=192 / P=320 ragged against the 128- and
+# 256-wide tiles. relu and
 # SwiGLU run in the same child (the mode is cached per process, the config
 # is not).
 RAGGED = dict(torch_dtype=4, sequence_len=512, num_experts=2, expert_top_k=2,
