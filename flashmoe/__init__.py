@@ -9,9 +9,11 @@ from flashmoe_amd import (  # noqa: F401
     get_weight_scales,
     initialize,
     moe_forward,
+    pack_weight_block_scales,
     pack_weight_scales,
     run_moe,
     set_score_bias,
+    set_weight_block_scales,
     set_weight_scales,
 )
 from flashmoe_amd import moe as _C  # noqa: F401  (the _C-equivalent surface)

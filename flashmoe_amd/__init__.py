@@ -13,8 +13,10 @@ from .moe import (  # noqa: F401
     get_weight_scales,
     initialize,
     moe_forward,
+    pack_weight_block_scales,
     pack_weight_scales,
     set_score_bias,
+    set_weight_block_scales,
     set_weight_scales,
 )
 from .ops import run_moe  # noqa: F401
@@ -33,4 +35,6 @@ __all__ = [
     "set_weight_scales",
     "get_weight_scales",
     "pack_weight_scales",
+    "set_weight_block_scales",
+    "pack_weight_block_scales",
 ]

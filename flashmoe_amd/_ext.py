@@ -63,6 +63,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_get_router.restype = ctypes.c_int
     lib.fm_set_weight_scales.argtypes = [p, ctypes.c_int32]
     lib.fm_set_weight_scales.restype = ctypes.c_int
+    lib.fm_set_weight_block_scales.argtypes = [p]
+    lib.fm_set_weight_block_scales.restype = ctypes.c_int
     lib.fm_get_weight_scales.argtypes = [ctypes.POINTER(p),
                                          ctypes.POINTER(ctypes.c_int32)]
     lib.fm_get_weight_scales.restype = ctypes.c_int

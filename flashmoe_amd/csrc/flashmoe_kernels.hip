@@ -51,6 +51,14 @@ struct fp8e4m3 { uint8_t v; };  // storage-only; dequant at fragment read
 
 // counted vmcnt wait with a compile-time literal (the triple-buffered
 // staging pipeline waits for tile t+1 while t+2's glds stay in flight)
+// kernels whose fp32 vector math must stay v_fma_f32 / v_mul_f32: no packed
+// fp32 instructions (a device-side target feature; the host pass has none)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FM_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define FM_NO_PK_F32
+#endif
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() {
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
@@ -1129,6 +1137,13 @@ struct GemmArgs {
                              // phase's base inside the per-expert record);
                              // wScaleGlu is the distance from there to the
                              // gating projection's vector (gated PHASE 0)
+  const float* bScale;       // fp8 weights (dtype 4): one fp32 scale per
+  long long bScaleStride;    // 128x128 block of B (fm_set_weight_block_scales,
+  int bScaleKB;              // DESIGN.md par.5m), read by the block-scale
+  int bScaleGlu;             // kernels only. bScale + we * bScaleStride is the
+                             // phase's grid [N/128][bScaleKB = K/128] inside
+                             // the expert's record; bScaleGlu is the distance
+                             // from there to the gating projection's grid
 };
 
 // Per-output-channel weight scale: W_eff[n, :] = s[n] *
@@ -1491,6 +1506,10 @@ constexpr int gemm_lds_bytes() {
 
 // compile-time bool handed to the epilogue's generic lambda
 template <bool B> struct BoolC { static constexpr bool value = B; };
+// compile-time int handed to the K-tile lambda
+template <int I> struct IntC { static constexpr int value = I; };
+// read-only data through the scalar cache (block scales)
+typedef __attribute__((address_space(4))) const float cas_f32;
 
 // Four consecutive output columns of one row (col0 .. col0+3, nValid of
 // them inside N) from one lane. Wide path: packed conversion + ONE 8-byte
@@ -1555,8 +1574,14 @@ __device__ __forceinline__ void storeRow8(ET* p, const uint32_t (&w)[4],
 // RT_SC1: honour a.sc1Out (agent-scope write-through epilogue stores).
 // Only the fused kernel has in-launch consumers, so only its walks
 // instantiate the sc1 epilogues; the classic kernels compile them out.
+// BS (fp8 weights, PHASE 0-2, classic kernels only): B
+// carries one fp32 scale per 128x128 block (a.bScale). A K block is two K
+// tiles: their MFMAs accumulate into a second fragment array, which one fp32
+// FMA per element folds into accv with the block's scale (accumulator
+// promotion). BS = false is the code without any of it.
 template <typename ET, int PHASE, int BN, int BM, typename WET, int STAGES,
-          int CK = 0, int CN = 0, bool RT_SC1 = false, bool GATED = false>
+          int CK = 0, int CN = 0, bool RT_SC1 = false, bool GATED = false,
+          bool BS = false>
 __device__ __forceinline__ bool gemm_job_body(
     const GemmArgs& a, char* smemBase, int e, int ksplit, int m0, int n0,
     int act, bool hasBias, int par, int jobLocal = 0) {
@@ -1738,6 +1763,28 @@ __device__ __forceinline__ bool gemm_job_body(
   // vmcnt(0)+barrier per tile (the drain is cheap: the stage had the
   // whole compute phase to land).
   const int nK = kLen / BK;
+  // BS: the wave's output columns lie in ONE 128-row block of B (tile
+  // origins are multiples of 128 and a wave spans BN/4 <= 64 columns), so a K
+  // block has one wave-uniform scale - two in the gated up phase, where even
+  // fragments are Wglu rows and odd ones Wup rows of the same P block. They
+  // are scalar loads from the read-only scale row s[n-block][0 .. K/128),
+  // issued one K block ahead: off the MFMA dependency chain, and no part of
+  // the vmcnt accounting of the staging pipeline.
+  cas_f32* bsRow = nullptr;
+  float sCur = 1.0f, sCurG = 1.0f;
+  if constexpr (BS) {
+    static_assert(BEZ == 1 && PHASE != 3 && !RT_SC1 && CK == 0,
+                  "block scales: fp8 weights, classic kernels");
+    // (a wave wholly past N in a ragged 256-wide tile reads the last block
+    // row, like its clamped B rows)
+    const int nCol = GATED ? min((n0 >> 1) + wc * (BN / 8), (N >> 1) - 1)
+                           : min(n0 + wc * (BN / 4), N - 1);
+    const int row = __builtin_amdgcn_readfirstlane((nCol >> 7) * a.bScaleKB +
+                                                   (kStart >> 7));
+    bsRow = (cas_f32*)(a.bScale + (size_t)we * a.bScaleStride) + row;
+    sCur = bsRow[0];
+    if constexpr (GATED) sCurG = bsRow[a.bScaleGlu];
+  }
   // (stage 0 was issued in the prologue above, B half first)
   if constexpr (SE == 3) {
     if (nK > 1) {
@@ -1765,85 +1812,196 @@ __device__ __forceinline__ bool gemm_job_body(
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   FM_STAMP(1);
-  for (int t = 0; t < nK; ++t) {
-    // STAGES==2: staggered staging - waves 0-3 stage tile t+1 before
-    // their first MFMA half, waves 4-7 between the halves, so on each
-    // SIMD the paired waves run complementary {stage issue | MFMA}
-    // segments instead of lockstep (microarch guide, two-waves-per-SIMD).
-    // STAGES==3: stage t+2 up front; the latency budget is two compute
-    // phases, so no stagger is needed.
-    const int pre = t + SE - 1;  // tile staged this iteration
-    const bool stageNow = pre < nK;
-    // stagger only pays on the wide (NF==4) stream; the BN=128 kernel's
-    // shorter MFMA halves lose more to the mid-stream insertion (measured)
-    const bool late = (SE == 2) && (NF == 4) && wave >= 4;
-    if (stageNow && !late) stage(pre * BK, pre % SE);
-    const ET* Al = Abase + (t % SE) * BM * BK;
-    const WET* Bl = Bbase + (t % SE) * BN * BK;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (s == 1 && late && stageNow) {
-        __builtin_amdgcn_s_setprio(0);
-        stage(pre * BK, pre % SE);
-        __builtin_amdgcn_s_setprio(1);
-      }
-      vec8 af[MI], bfr[NF];
-      const int rl = lane & 15;
-      const int cbase = 4 * s + (lane >> 4);
-      auto aread = [&](int mi) {
-        const int R = wr * (BM / 2) + mi * 16 + rl;
-        af[mi] = *reinterpret_cast<const vec8*>(
-            &Al[R * BK + ((cbase ^ (R & 7)) * 8)]);
-      };
-      // Round-robin reads and MFMAs, pinned with sched_barrier(0): each
-      // MFMA pair then waits (partial lgkmcnt) only on fragments read a
-      // group earlier, instead of the scheduler's whole-segment
-      // lgkmcnt(0) drain before the first MFMA (seen in the .s).
-#pragma unroll
-      for (int ni = 0; ni < NF; ++ni) {
-        const int R = wc * (BN / 4) + ni * 16 + rl;
-        if constexpr (BEZ == 1) {
-          const int c16 = (cbase >> 1) ^ ((R >> 2) & 3);
-          const uint32_t* bp = reinterpret_cast<const uint32_t*>(
-              (const char*)Bl + (size_t)R * BK + c16 * 16 + (cbase & 1) * 8);
-          bfr[ni] = dequant_fp8x8_bf16(bp[0], bp[1]);
-        } else {
-          bfr[ni] = *reinterpret_cast<const vec8*>(
-              &Bl[R * BK + ((cbase ^ (R & 7)) * 8)]);
+  if constexpr (BS) {
+    // The K tile of the loop below, in two forms: MODE 1 is the first tile of
+    // a K block (its first MFMA per fragment takes a zero C operand, so part
+    // needs no clear), MODE 2 the second, which folds part into accv.
+    f32x4 part[MI][NF];
+    float sNxt = sCur, sNxtG = sCurG;
+    auto tile = [&](int t, auto modec) __attribute__((always_inline)) {
+      constexpr int MODE = decltype(modec)::value;
+      // STAGES==2: staggered staging - waves 0-3 stage tile t+1 before
+      // their first MFMA half, waves 4-7 between the halves, so on each
+      // SIMD the paired waves run complementary {stage issue | MFMA}
+      // segments instead of lockstep (microarch guide, two-waves-per-SIMD).
+      // STAGES==3: stage t+2 up front; the latency budget is two compute
+      // phases, so no stagger is needed.
+      const int pre = t + SE - 1;  // tile staged this iteration
+      const bool stageNow = pre < nK;
+      // stagger only pays on the wide (NF==4) stream; the BN=128 kernel's
+      // shorter MFMA halves lose more to the mid-stream insertion (measured)
+      const bool late = (SE == 2) && (NF == 4) && wave >= 4;
+      if (stageNow && !late) stage(pre * BK, pre % SE);
+      const ET* Al = Abase + (t % SE) * BM * BK;
+      const WET* Bl = Bbase + (t % SE) * BN * BK;
+      __builtin_amdgcn_s_setprio(1);
+  #pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (s == 1 && late && stageNow) {
+          __builtin_amdgcn_s_setprio(0);
+          stage(pre * BK, pre % SE);
+          __builtin_amdgcn_s_setprio(1);
         }
-      }
-      aread(0);
-      aread(1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int g2 = 0; g2 < MI / 2; ++g2) {
-        if (g2 < MI / 2 - 1) {
-          aread(2 * g2 + 2);
-          aread(2 * g2 + 3);
+        vec8 af[MI], bfr[NF];
+        const int rl = lane & 15;
+        const int cbase = 4 * s + (lane >> 4);
+        auto aread = [&](int mi) {
+          const int R = wr * (BM / 2) + mi * 16 + rl;
+          af[mi] = *reinterpret_cast<const vec8*>(
+              &Al[R * BK + ((cbase ^ (R & 7)) * 8)]);
+        };
+        // Round-robin reads and MFMAs, pinned with sched_barrier(0): each
+        // MFMA pair then waits (partial lgkmcnt) only on fragments read a
+        // group earlier, instead of the scheduler's whole-segment
+        // lgkmcnt(0) drain before the first MFMA (seen in the .s).
+  #pragma unroll
+        for (int ni = 0; ni < NF; ++ni) {
+          const int R = wc * (BN / 4) + ni * 16 + rl;
+          if constexpr (BEZ == 1) {
+            const int c16 = (cbase >> 1) ^ ((R >> 2) & 3);
+            const uint32_t* bp = reinterpret_cast<const uint32_t*>(
+                (const char*)Bl + (size_t)R * BK + c16 * 16 + (cbase & 1) * 8);
+            bfr[ni] = dequant_fp8x8_bf16(bp[0], bp[1]);
+          } else {
+            bfr[ni] = *reinterpret_cast<const vec8*>(
+                &Bl[R * BK + ((cbase ^ (R & 7)) * 8)]);
+          }
         }
-#pragma unroll
-        for (int mi = 2 * g2; mi < 2 * g2 + 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < NF; ++ni)
-            // operands swapped (B fragment first): the accumulator then
-            // holds C^T's layout - lane & 15 is the output ROW and
-            // 4 * (lane >> 4) + r are four CONSECUTIVE output columns, so
-            // the epilogue stores a row's columns as one wide word. Same
-            // dot products in the same K order.
-            accv[mi][ni] = ETr<ET>::mfma(bfr[ni], af[mi], accv[mi][ni]);
+        aread(0);
+        aread(1);
         __builtin_amdgcn_sched_barrier(0);
+  #pragma unroll
+        for (int g2 = 0; g2 < MI / 2; ++g2) {
+          if (g2 < MI / 2 - 1) {
+            aread(2 * g2 + 2);
+            aread(2 * g2 + 3);
+          }
+  #pragma unroll
+          for (int mi = 2 * g2; mi < 2 * g2 + 2; ++mi)
+  #pragma unroll
+            for (int ni = 0; ni < NF; ++ni)
+              // operands swapped (B fragment first): the accumulator then
+              // holds C^T's layout - lane & 15 is the output ROW and
+              // 4 * (lane >> 4) + r are four CONSECUTIVE output columns, so
+              // the epilogue stores a row's columns as one wide word. Same
+              // dot products in the same K order.
+              part[mi][ni] = ETr<ET>::mfma(
+                  bfr[ni], af[mi],
+                  (MODE == 1 && s == 0) ? f32x4{0.f, 0.f, 0.f, 0.f}
+                                        : part[mi][ni]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
+      if constexpr (MODE == 2) {
+  #pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+  #pragma unroll
+          for (int ni = 0; ni < NF; ++ni)
+            accv[mi][ni] +=
+                ((GATED && (ni & 1) == 0) ? sCurG : sCur) * part[mi][ni];
+      }
+      __builtin_amdgcn_s_setprio(0);
+      if constexpr (SE == 3) {
+        // only t+1 must have landed; t+2 (the GPT glds issued this
+        // iteration) may still be in flight
+        if (stageNow) wait_vmcnt<GPT>(); else wait_vmcnt<0>();
+      } else {
+        wait_vmcnt<0>();  // t+1 landed
+      }
+      __builtin_amdgcn_s_barrier();  // readers done AND next tile ready
+    };
+    // kLen is a multiple of 128 (host-checked), so nK is even
+    for (int t = 0; t < nK; t += 2) {
+      if (t + 2 < nK) {
+        sNxt = bsRow[(t >> 1) + 1];
+        if constexpr (GATED) sNxtG = bsRow[a.bScaleGlu + (t >> 1) + 1];
+      }
+      tile(t, IntC<1>{});
+      tile(t + 1, IntC<2>{});
+      sCur = sNxt;
+      sCurG = sNxtG;
     }
-    __builtin_amdgcn_s_setprio(0);
-    if constexpr (SE == 3) {
-      // only t+1 must have landed; t+2 (the GPT glds issued this
-      // iteration) may still be in flight
-      if (stageNow) wait_vmcnt<GPT>(); else wait_vmcnt<0>();
-    } else {
-      wait_vmcnt<0>();  // t+1 landed
+  } else {
+    for (int t = 0; t < nK; ++t) {
+      // STAGES==2: staggered staging - waves 0-3 stage tile t+1 before
+      // their first MFMA half, waves 4-7 between the halves, so on each
+      // SIMD the paired waves run complementary {stage issue | MFMA}
+      // segments instead of lockstep (microarch guide, two-waves-per-SIMD).
+      // STAGES==3: stage t+2 up front; the latency budget is two compute
+      // phases, so no stagger is needed.
+      const int pre = t + SE - 1;  // tile staged this iteration
+      const bool stageNow = pre < nK;
+      // stagger only pays on the wide (NF==4) stream; the BN=128 kernel's
+      // shorter MFMA halves lose more to the mid-stream insertion (measured)
+      const bool late = (SE == 2) && (NF == 4) && wave >= 4;
+      if (stageNow && !late) stage(pre * BK, pre % SE);
+      const ET* Al = Abase + (t % SE) * BM * BK;
+      const WET* Bl = Bbase + (t % SE) * BN * BK;
+      __builtin_amdgcn_s_setprio(1);
+  #pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        if (s == 1 && late && stageNow) {
+          __builtin_amdgcn_s_setprio(0);
+          stage(pre * BK, pre % SE);
+          __builtin_amdgcn_s_setprio(1);
+        }
+        vec8 af[MI], bfr[NF];
+        const int rl = lane & 15;
+        const int cbase = 4 * s + (lane >> 4);
+        auto aread = [&](int mi) {
+          const int R = wr * (BM / 2) + mi * 16 + rl;
+          af[mi] = *reinterpret_cast<const vec8*>(
+              &Al[R * BK + ((cbase ^ (R & 7)) * 8)]);
+        };
+        // Round-robin reads and MFMAs, pinned with sched_barrier(0): each
+        // MFMA pair then waits (partial lgkmcnt) only on fragments read a
+        // group earlier, instead of the scheduler's whole-segment
+        // lgkmcnt(0) drain before the first MFMA (seen in the .s).
+  #pragma unroll
+        for (int ni = 0; ni < NF; ++ni) {
+          const int R = wc * (BN / 4) + ni * 16 + rl;
+          if constexpr (BEZ == 1) {
+            const int c16 = (cbase >> 1) ^ ((R >> 2) & 3);
+            const uint32_t* bp = reinterpret_cast<const uint32_t*>(
+                (const char*)Bl + (size_t)R * BK + c16 * 16 + (cbase & 1) * 8);
+            bfr[ni] = dequant_fp8x8_bf16(bp[0], bp[1]);
+          } else {
+            bfr[ni] = *reinterpret_cast<const vec8*>(
+                &Bl[R * BK + ((cbase ^ (R & 7)) * 8)]);
+          }
+        }
+        aread(0);
+        aread(1);
+        __builtin_amdgcn_sched_barrier(0);
+  #pragma unroll
+        for (int g2 = 0; g2 < MI / 2; ++g2) {
+          if (g2 < MI / 2 - 1) {
+            aread(2 * g2 + 2);
+            aread(2 * g2 + 3);
+          }
+  #pragma unroll
+          for (int mi = 2 * g2; mi < 2 * g2 + 2; ++mi)
+  #pragma unroll
+            for (int ni = 0; ni < NF; ++ni)
+              // operands swapped (B fragment first): the accumulator then
+              // holds C^T's layout - lane & 15 is the output ROW and
+              // 4 * (lane >> 4) + r are four CONSECUTIVE output columns, so
+              // the epilogue stores a row's columns as one wide word. Same
+              // dot products in the same K order.
+              accv[mi][ni] = ETr<ET>::mfma(bfr[ni], af[mi], accv[mi][ni]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      if constexpr (SE == 3) {
+        // only t+1 must have landed; t+2 (the GPT glds issued this
+        // iteration) may still be in flight
+        if (stageNow) wait_vmcnt<GPT>(); else wait_vmcnt<0>();
+      } else {
+        wait_vmcnt<0>();  // t+1 landed
+      }
+      __builtin_amdgcn_s_barrier();  // readers done AND next tile ready
     }
-    __builtin_amdgcn_s_barrier();  // readers done AND next tile ready
   }
 
   FM_STAMP(2);
@@ -1879,7 +2037,7 @@ __device__ __forceinline__ bool gemm_job_body(
   // 2j is g and 2j+1 is u of P columns pBase + j*16 + r, so the pair takes
   // s_glu and s_up of the same columns. K-split partials each take the
   // factor (it distributes over their sum).
-  constexpr bool WS = (BEZ == 1) && (PHASE != 3);
+  constexpr bool WS = (BEZ == 1) && (PHASE != 3) && !BS;
   float sv[WS ? NF : 1][4];
   if constexpr (WS) {
     const float* sp =
@@ -2178,6 +2336,44 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_bf16_big(GemmArgs a) {
                                    (PHASE == 0 && ACT >= 2)>(
         a, smem, e, ksplit, (rem % mT) * BM, (rem / mT) * BN, ACT, HAS_BIAS,
         par, (jl - lin0) / gstride);
+    par ^= ran ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Block-scale sibling of k_group_gemm_bf16_big: bf16
+// activations, fp8 e4m3 weights with one fp32 scale per 128x128 block, the
+// BS body of gemm_job_body, PHASE 0-2. The same remap loop. The second
+// fragment array doubles the accumulator registers, so the host launches it
+// for the 256x128, 128x256 and 128x128 tiles only. The promotion's fp32 FMAs
+// stay scalar (v_fma_f32): the packed fp32 forms are switched off here.
+// ---------------------------------------------------------------------------
+template <int PHASE, int ACT, bool HAS_BIAS, int BN, int BM, int STAGES>
+__global__ __launch_bounds__(512, 2)
+FM_NO_PK_F32
+void k_group_gemm_bs_big(GemmArgs a) {
+  static_assert(BM * BN < 256 * 256, "no room for part[][] in the 256x256 tile");
+  __shared__ __attribute__((aligned(16))) char smem[
+      gemm_lds_bytes<BM, BN, 1, STAGES>()];
+  const int mT = a.totalJobs > 0 ? a.jobsMT : gridDim.x;
+  const int nT = a.totalJobs > 0 ? a.jobsNT : gridDim.y;
+  const int gstride = gridDim.x * gridDim.y * gridDim.z;
+  const int nBlocks = a.totalJobs > 0 ? a.totalJobs : gstride;
+  const int lin0 =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int qx = nBlocks / 8, rx = nBlocks % 8;
+  int par = 0;
+  for (int jl = lin0; jl < nBlocks; jl += gstride) {
+    const int xcd = jl % 8, pos = jl / 8;
+    const int swz = a.noRemap
+        ? jl
+        : (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+    const int e = swz / (mT * nT);  // block-scaled launches never split K
+    const int rem = swz % (mT * nT);
+    const bool ran = gemm_job_body<bf16, PHASE, BN, BM, fp8e4m3, STAGES, 0, 0,
+                                   false, (PHASE == 0 && ACT >= 2), true>(
+        a, smem, e, 0, (rem % mT) * BM, (rem / mT) * BN, ACT, HAS_BIAS, par,
+        (jl - lin0) / gstride);
     par ^= ran ? 1 : 0;
   }
 }
@@ -2746,10 +2942,16 @@ constexpr int kDecodeFfnMaxSFp8 = 16;
 // the register count of four waves per SIMD (LDS allows four blocks per CU);
 // the floor keeps the allocator there for their WS siblings, whose epilogue
 // carries one more value. Every other instantiation keeps the default.
-template <typename ET, typename WET, int PHASE, bool GATED, bool WS = false>
-__global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu((WS && !GATED) ? 4 : 1)))
-void k_decode_ffn(GemmArgs a) {
+// The body's WS is 0 none / 1 per channel / 2 per 128x128 block (DESIGN.md
+// par.5m, k_decode_ffn_bs below): a wave's 128-element chunk is exactly one K
+// block and the block's 16 weight rows lie in one output block, so a chunk's
+// MFMAs accumulate into a temporary set that one fp32 FMA per element folds
+// into acc with the chunk's scale (one per matrix), loaded beside the chunk's
+// B prefetch. Reduction and epilogue are those of WS = 0. The temporary set
+// puts the ungated kernels at 134-136 VGPRs, three waves per SIMD: under the
+// four-wave floor they spill to scratch, so they carry no floor.
+template <typename ET, typename WET, int PHASE, bool GATED, int WS>
+__device__ __forceinline__ void decode_ffn_body(const GemmArgs& a) {
   using vec8 = typename ETr<ET>::vec8;
   constexpr int BEZ = (int)sizeof(WET);
   constexpr int KPL = 16 / BEZ;               // K elements per 16-B load
@@ -2791,13 +2993,22 @@ void k_decode_ffn(GemmArgs a) {
   // WS: the weight scale(s) of this block's column, loaded once per block by
   // the wave that runs the epilogue (s0: the one matrix / u, s1: g)
   float s0 = 1.0f, s1 = 1.0f;
-  if constexpr (WS) {
+  if constexpr (WS == 1) {
     static_assert(BEZ == 1, "weight scales belong to fp8 weights");
     if (wave == 0) {
       const float* sp = a.wScale + (size_t)we * a.wScaleStride + n0 + rl;
       s0 = sp[0];
       if constexpr (GATED) s1 = sp[a.wScaleGlu];
     }
+  }
+  // WS 2: this block's scale row(s) [K/128] (0: Wup or the one matrix, 1: g)
+  // read through the scalar cache (read-only data, wave-uniform index)
+  cas_f32* bsp[NM];
+  if constexpr (WS == 2) {
+    static_assert(BEZ == 1, "weight scales belong to fp8 weights");
+    bsp[0] = (cas_f32*)(a.bScale + (size_t)we * a.bScaleStride +
+                        (size_t)(n0 >> 7) * a.bScaleKB);
+    if constexpr (GATED) bsp[1] = bsp[0] + a.bScaleGlu;
   }
 
   for (int mg0 = 0; mg0 < (int)routed; mg0 += kDecRows) {
@@ -2839,17 +3050,23 @@ void k_decode_ffn(GemmArgs a) {
             areg[i];
       }
     };
-    auto loadB = [&](u32x4 (&b)[NM][NLD], int kc) __attribute__((always_inline)) {
+    auto loadB = [&](u32x4 (&b)[NM][NLD], float (&bs)[NM],
+                     int kc) __attribute__((always_inline)) {
 #pragma unroll
-      for (int mt = 0; mt < NM; ++mt)
+      for (int mt = 0; mt < NM; ++mt) {
+        if constexpr (WS == 2)  // kc < K here
+          bs[mt] = bsp[mt][__builtin_amdgcn_readfirstlane(kc >> 7)];
 #pragma unroll
         for (int j = 0; j < NLD; ++j) {
           const int k = kc + j * 4 * KPL;  // wave-uniform; K % 64 == 0
           b[mt][j] = u32x4{0u, 0u, 0u, 0u};
           if (k < K) b[mt][j] = *reinterpret_cast<const u32x4*>(Bw[mt] + k);
         }
+      }
     };
-    auto compute = [&](const u32x4 (&b)[NM][NLD]) __attribute__((always_inline)) {
+    auto compute = [&](const u32x4 (&b)[NM][NLD],
+                       const float (&bs)[NM]) __attribute__((always_inline)) {
+      f32x4 tmp[NM][2];  // WS 2: the chunk's unscaled sums
 #pragma unroll
       for (int j = 0; j < NLD; ++j)
 #pragma unroll
@@ -2867,10 +3084,26 @@ void k_decode_ffn(GemmArgs a) {
               bf = dequant_fp8x8_bf16(b[mt][j][2 * s], b[mt][j][2 * s + 1]);
             else
               bf = __builtin_bit_cast(vec8, b[mt][j]);
-            acc[mt][0] = ETr<ET>::mfma(a0, bf, acc[mt][0]);
-            if (two) acc[mt][1] = ETr<ET>::mfma(a1, bf, acc[mt][1]);
+            if constexpr (WS == 2) {
+              // the chunk's first MFMA takes a zero C operand
+              const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+              const bool first = j == 0 && s == 0;
+              tmp[mt][0] = ETr<ET>::mfma(a0, bf, first ? z : tmp[mt][0]);
+              if (two)
+                tmp[mt][1] = ETr<ET>::mfma(a1, bf, first ? z : tmp[mt][1]);
+            } else {
+              acc[mt][0] = ETr<ET>::mfma(a0, bf, acc[mt][0]);
+              if (two) acc[mt][1] = ETr<ET>::mfma(a1, bf, acc[mt][1]);
+            }
           }
         }
+      if constexpr (WS == 2) {
+#pragma unroll
+        for (int mt = 0; mt < NM; ++mt) {
+          acc[mt][0] += bs[mt] * tmp[mt][0];
+          if (two) acc[mt][1] += bs[mt] * tmp[mt][1];
+        }
+      }
     };
     // the A region is private to the wave: LDS serves a wave's accesses in
     // order, so a wavefront-scope fence orders its stores and fragment reads
@@ -2879,15 +3112,16 @@ void k_decode_ffn(GemmArgs a) {
       __builtin_amdgcn_wave_barrier();
     };
     // consume chunk kc from bc; prefetch chunk kc + 4 * kDecBK into bn
-    auto step = [&](const u32x4 (&bc)[NM][NLD], u32x4 (&bn)[NM][NLD],
+    auto step = [&](const u32x4 (&bc)[NM][NLD], const float (&sc)[NM],
+                    u32x4 (&bn)[NM][NLD], float (&sn)[NM],
                     int kc) __attribute__((always_inline)) {
       const int kn = kc + 4 * kDecBK;
       const bool more = kn < K;
       if (more) {
         loadA(kn);
-        loadB(bn, kn);
+        loadB(bn, sn, kn);
       }
-      compute(bc);
+      compute(bc, sc);
       if (more) {
         waveSync();
         storeA();
@@ -2895,15 +3129,16 @@ void k_decode_ffn(GemmArgs a) {
       }
     };
     u32x4 b0[NM][NLD], b1[NM][NLD];
+    float sb0[NM], sb1[NM];  // WS 2: the block scales of b0 / b1
     const int kc0 = wave * kDecBK;
     if (kc0 < K) {
       loadA(kc0);
-      loadB(b0, kc0);
+      loadB(b0, sb0, kc0);
       storeA();
       waveSync();
       for (int kc = kc0; kc < K; kc += 8 * kDecBK) {
-        step(b0, b1, kc);
-        if (kc + 4 * kDecBK < K) step(b1, b0, kc + 4 * kDecBK);
+        step(b0, sb0, b1, sb1, kc);
+        if (kc + 4 * kDecBK < K) step(b1, sb1, b0, sb0, kc + 4 * kDecBK);
       }
     }
 
@@ -2932,7 +3167,7 @@ void k_decode_ffn(GemmArgs a) {
         bv = toF(reinterpret_cast<const ET*>(a.bias)[(size_t)we * N + col]);
       // WS: the reduced sums take the column's weight scale(s) in place
       // (acc[0]: the one matrix / u, acc[1]: g)
-      if constexpr (WS) {
+      if constexpr (WS == 1) {
 #pragma unroll
         for (int f = 0; f < 2; ++f)
 #pragma unroll
@@ -2988,6 +3223,22 @@ void k_decode_ffn(GemmArgs a) {
     }
     __syncthreads();  // the next pass restages over the reduction slabs
   }
+}
+
+template <typename ET, typename WET, int PHASE, bool GATED, bool WS = false>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu((WS && !GATED) ? 4 : 1)))
+void k_decode_ffn(GemmArgs a) {
+  decode_ffn_body<ET, WET, PHASE, GATED, WS ? 1 : 0>(a);
+}
+
+// block scales: bf16 activations, fp8 e4m3 weights. The promotion's fp32 FMAs
+// stay scalar (v_fma_f32): the packed fp32 forms are switched off here.
+template <int PHASE, bool GATED>
+__global__ __launch_bounds__(256)
+FM_NO_PK_F32
+void k_decode_ffn_bs(GemmArgs a) {
+  decode_ffn_body<bf16, fp8e4m3, PHASE, GATED, 2>(a);
 }
 
 // sum the k non-atomic combine slots (kept-masked) into the output
@@ -3902,10 +4153,29 @@ struct State {
   // (fm_set_weight_scales): borrowed device tensor
   // [nLx + nSh, P + H (+ P gated)], record = [s_up | s_dn | s_glu]
   const float* wScale = nullptr;
-  int wScaleGran = 0;        // 0 none, 1 per output channel
+  // or one fp32 scale per 128x128 weight block (fm_set_weight_block_scales,
+  // DESIGN.md par.5m): borrowed device tensor [nLx + nSh, (2 or 3) * PB * HB],
+  // record = [s_up (PB x HB) | s_dn (HB x PB) | s_glu (PB x HB)]. At most one
+  // of wScale / bScale is set.
+  const float* bScale = nullptr;
+  int wScaleGran = 0;        // 0 none, 1 per output channel, 2 per block
   uint32_t wScaleGen = 0;    // bumped per set call: part of the graph key
 };
 State g;
+
+// The same for block scales: the phase's grid [N/128][K/128] inside the
+// record of weight expert `firstExpert`. Null without block scales.
+static void setBlockScaleArgs(GemmArgs& a, int phase, int firstExpert,
+                              bool strided) {
+  const long long grid = (long long)(g.P / 128) * (g.H / 128);
+  const long long BSC = (g.gated ? 3 : 2) * grid;
+  a.bScale = g.bScale ? g.bScale + (size_t)firstExpert * BSC +
+                            (phase == 0 ? 0 : grid)
+                      : nullptr;
+  a.bScaleStride = strided ? BSC : 0;
+  a.bScaleKB = (phase == 0 ? g.H : g.P) / 128;
+  a.bScaleGlu = (int)(2 * grid);  // s_up -> s_glu (gated up phase)
+}
 
 // Point a launch at the weight scales of its phase (0 up, 1 down): the
 // record of weight expert `firstExpert`, offset to the phase's vector. The
@@ -3919,6 +4189,7 @@ static void setWeightScaleArgs(GemmArgs& a, int phase, int firstExpert,
                       : nullptr;
   a.wScaleStride = strided ? SC : 0;
   a.wScaleGlu = g.P + g.H;  // s_up -> s_glu inside a record (gated up phase)
+  setBlockScaleArgs(a, phase, firstExpert, strided);
 }
 
 // kernel-side view of g.router
@@ -4467,6 +4738,7 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   g.router = State{}.router;  // a fresh config starts from the default router
   g.routerRV = false;
   g.wScale = nullptr;  // and without weight scales
+  g.bScale = nullptr;
   g.wScaleGran = 0;
   g.cfg = *cfg;
   g.rank = rank;
@@ -4819,8 +5091,9 @@ int fm_set_router(const fm_router_config* r) {
 int fm_set_weight_scales(const float* scales, int32_t granularity) {
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
   if (granularity == 2) {
-    setErr("weight scale granularity 2 (128x128 blocks) is reserved: block "
-           "scales vary along K and need in-loop handling (DESIGN.md 5l)");
+    setErr("weight scale granularity 2 (128x128 blocks) is reserved here: "
+           "this call's record cannot describe blocks; attach them with "
+           "fm_set_weight_block_scales (DESIGN.md 5m)");
     return FM_ERR_UNSUPPORTED;
   }
   if (granularity != 0 && granularity != 1) {
@@ -4840,14 +5113,40 @@ int fm_set_weight_scales(const float* scales, int32_t granularity) {
     return FM_ERR_STATE;
   }
   g.wScale = granularity == 1 ? scales : nullptr;
+  g.bScale = nullptr;  // one kind of scale at a time
   g.wScaleGran = granularity;
+  ++g.wScaleGen;  // never replay a forward captured under other scales
+  return FM_OK;
+}
+
+int fm_set_weight_block_scales(const float* scales) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (scales && g.cfg.dtype != 4) {
+    snprintf(g_err, sizeof(g_err),
+             "weight block scales need fp8 expert weights with bf16 "
+             "activations: torch_dtype must be 4, the config has torch_dtype "
+             "%d%s", (int)g.cfg.dtype,
+             g.cfg.dtype == 5 ? " (block scales on the MX path are not built)"
+                              : "");
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (scales && (g.H % 128 != 0 || g.P % 128 != 0)) {
+    snprintf(g_err, sizeof(g_err),
+             "weight block scales need hidden_size and intermediate_size to "
+             "be multiples of the 128x128 block; got hidden_size %d, "
+             "intermediate_size %d", g.H, g.P);
+    return FM_ERR_UNSUPPORTED;
+  }
+  g.bScale = scales;
+  g.wScale = nullptr;  // one kind of scale at a time
+  g.wScaleGran = scales ? 2 : 0;
   ++g.wScaleGen;  // never replay a forward captured under other scales
   return FM_OK;
 }
 
 int fm_get_weight_scales(const float** scales, int32_t* granularity) {
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
-  if (scales) *scales = g.wScale;
+  if (scales) *scales = g.bScale ? g.bScale : g.wScale;
   if (granularity) *granularity = g.wScaleGran;
   return FM_OK;
 }
@@ -4991,6 +5290,19 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
     else if (M >= 128 && h128 >= 256) mode = 4;
     else mode = 2;
     if (forceMode >= 0) mode = forceMode;
+    // block scales (par.5m): the second fragment array does not fit the
+    // 256x256 tile, and the small synchronous kernel has no variant, so such
+    // a launch runs mode 1, 3 or 4. The thresholds above do not carry over:
+    // with part[][] the 128x128 kernel holds 130-135 VGPRs and runs ONE block
+    // per CU, which takes away what made it the first choice, and the
+    // 128x256 tile measured fastest or tied on all three model shapes
+    // (profiles/r11_block_scale_modes.txt). So: 128x256 where its grid fills
+    // the chip, else 256x128 where that one does, else 128x128 (it clamps
+    // ragged rows like mode 2). FM_FORCE_MODE 1, 3 and 4 are honoured; a
+    // forced 0 or 2 takes this choice.
+    const bool bs = a.bScale != nullptr && phase != 3;
+    if (bs && mode != 1 && mode != 3 && (mode != 4 || forceMode != 4))
+      mode = (M >= 128 && h256 >= 256) ? 3 : (M >= 256 && b128n >= 256) ? 1 : 4;
     GemmArgs aa = a;
     aa.N = N;
     aa.gluOffset = gluOffset;
@@ -5019,7 +5331,8 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
     }();
     if (persist && mode != 2) {
       const int jm = grid.x, jn = grid.y, J = jm * jn * nE * skf;
-      int resident = (mode == 4) ? 512 : 256;
+      // (the block-scale 128x128 kernel holds 130-135 VGPRs: one block/CU)
+      int resident = (mode == 4 && !bs) ? 512 : 256;
       if (persistCap > 0) resident = std::min(resident, persistCap);
       if (J > resident) {
         aa.totalJobs = J;
@@ -5141,9 +5454,23 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
         hipLaunchKernelGGL((k_group_gemm_bf16<ET, PH, AC, HB, WET>), grid,    \
                            block, 0, st, aa);                                 \
     } while (0)
+    // block scales: the default STAGES of modes 1, 3 and 4
+#define GG_BS(PH, AC, HB)                                                     \
+    do {                                                                      \
+      if (mode == 1)                                                          \
+        hipLaunchKernelGGL((k_group_gemm_bs_big<PH, AC, HB, 128, 256, 3>),    \
+                           grid, block, 0, st, aa);                           \
+      else if (mode == 3)                                                     \
+        hipLaunchKernelGGL((k_group_gemm_bs_big<PH, AC, HB, 256, 128, 3>),    \
+                           grid, block, 0, st, aa);                           \
+      else  /* mode 4 */                                                      \
+        hipLaunchKernelGGL((k_group_gemm_bs_big<PH, AC, HB, 128, 128, 2>),    \
+                           grid, block, 0, st, aa);                           \
+    } while (0)
 #define GG_CASE(PH, AC, HB)                                                   \
     do {                                                                      \
-      if (g.cfg.dtype == 3) GG_ET(fp16, PH, AC, HB, fp16);                    \
+      if (bs) GG_BS(PH, AC, HB);                                              \
+      else if (g.cfg.dtype == 3) GG_ET(fp16, PH, AC, HB, fp16);               \
       else if (g.cfg.dtype == 4) GG_ET(bf16, PH, AC, HB, fp8e4m3);            \
       else GG_ET(bf16, PH, AC, HB, bf16);                                     \
     } while (0)
@@ -5164,6 +5491,7 @@ static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
         break;
     }
 #undef GG_CASE
+#undef GG_BS
   } else {
     dim3 block(256);
     dim3 grid(DIVUP(M, 64), DIVUP(N, 64), nE);
@@ -5238,7 +5566,15 @@ static int launch_decode_ffn(hipStream_t st, int phase, const GemmArgs& a,
       hipLaunchKernelGGL((k_decode_ffn<ET, WET, 0, false, WS>), grid, block,  \
                          0, st, aa);                                          \
   } while (0)
-  if (g.cfg.dtype == 3) DEC_ET(fp16, fp16, false);
+  if (g.cfg.dtype == 4 && aa.bScale) {  // block scales (par.5m)
+    if (phase == 1)
+      hipLaunchKernelGGL((k_decode_ffn_bs<1, false>), grid, block, 0, st, aa);
+    else if (gated)
+      hipLaunchKernelGGL((k_decode_ffn_bs<0, true>), grid, block, 0, st, aa);
+    else
+      hipLaunchKernelGGL((k_decode_ffn_bs<0, false>), grid, block, 0, st, aa);
+  }
+  else if (g.cfg.dtype == 3) DEC_ET(fp16, fp16, false);
   else if (g.cfg.dtype == 4 && aa.wScale) DEC_ET(bf16, fp8e4m3, true);
   else if (g.cfg.dtype == 4) DEC_ET(bf16, fp8e4m3, false);
   else DEC_ET(bf16, bf16, false);
@@ -5336,7 +5672,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // taught about them, its GemmArgs carry none)
   if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
       g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV &&
-      !g.wScale) {
+      !g.wScale && !g.bScale) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -5465,7 +5801,7 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                       (uint64_t)(decodeFfnMode() + 1) << 38 |
                       (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
                       (fusedEnabled() ? 1 : 0))),
-                  const_cast<float*>(g.wScale),
+                  const_cast<float*>(g.bScale ? g.bScale : g.wScale),
                   reinterpret_cast<void*>(static_cast<uintptr_t>(g.wScaleGen))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;

@@ -22,7 +22,9 @@ _state = {
     "gate_out": None,  # persistent [S, PX] buffer (internal, like the
     # reference's flat-buffer gate output, python_bindings.cu:70-74)
     "score_bias": None,  # the fp32 [E] tensor fm_set_router borrows
-    "weight_scales": None,  # the fp32 tensor fm_set_weight_scales borrows
+    # the fp32 tensor fm_set_weight_scales / fm_set_weight_block_scales
+    # borrows (one kind is attached at a time)
+    "weight_scales": None,
 }
 
 
@@ -209,6 +211,61 @@ def set_weight_scales(scales):
     _state["weight_scales"] = scales
 
 
+def _weight_block_scale_shape():
+    """(records, BSC) of the block-scale tensor for the initialized config:
+    one record [s_up (PB x HB) | s_dn (HB x PB) | s_glu (PB x HB, gated only)]
+    per local routed expert, then one per shared expert."""
+    cfg = _state["cfg"]
+    grid = (cfg["intermediate_size"] // 128) * (cfg["hidden_size"] // 128)
+    n = _ext.load().fm_get_num_local_experts() + num_shared(cfg)
+    return n, expert_mats(cfg["hidden_act"]) * grid
+
+
+def set_weight_block_scales(scales):
+    """Attach (or, with None, detach) one fp32 scale per 128x128 block of the
+    fp8 expert weights (torch_dtype 4): W_eff[r, c] = W_fp8[r, c] *
+    s[r // 128][c // 128], the layout of the DeepSeek-V3 / Qwen3 FP8
+    checkpoints. `scales` is a contiguous float32 CUDA
+    tensor [nLx + nSh, BSC] as built by pack_weight_block_scales. Attaching
+    detaches per-channel scales, and the reverse. The tensor is borrowed by
+    the library and kept alive here; its contents may be rewritten in place
+    between forwards."""
+    import torch
+
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    lib = _ext.load()
+    if scales is None:
+        _ext.check(lib.fm_set_weight_block_scales(None),
+                   "fm_set_weight_block_scales")
+        _state["weight_scales"] = None
+        return
+    cfg = _state["cfg"]
+    if cfg["torch_dtype"] != 4:
+        raise ValueError(
+            f"weight block scales need fp8 expert weights with bf16 "
+            f"activations (torch_dtype 4); the initialized config has "
+            f"torch_dtype {cfg['torch_dtype']}")
+    if cfg["hidden_size"] % 128 or cfg["intermediate_size"] % 128:
+        raise ValueError(
+            f"weight block scales need hidden_size and intermediate_size to be "
+            f"multiples of 128; got {cfg['hidden_size']} and "
+            f"{cfg['intermediate_size']}")
+    want = _weight_block_scale_shape()
+    if not isinstance(scales, torch.Tensor) or not scales.is_cuda or \
+            scales.dtype != torch.float32 or tuple(scales.shape) != want or \
+            not scales.is_contiguous():
+        got = (f"{scales.dtype} {list(scales.shape)} on {scales.device}"
+               if isinstance(scales, torch.Tensor) else type(scales).__name__)
+        raise ValueError(
+            f"weight block scales must be a contiguous CUDA float32 tensor of "
+            f"shape [nLx + nSh, BSC] = {list(want)}; got {got}")
+    _ext.check(
+        lib.fm_set_weight_block_scales(ctypes.c_void_p(scales.data_ptr())),
+        "fm_set_weight_block_scales")
+    _state["weight_scales"] = scales
+
+
 def get_weight_scales():
     """The attached weight-scale tensor, or None, as the library reports it
     (fm_get_weight_scales). Scales attached through the raw C-ABI are not a
@@ -225,8 +282,9 @@ def get_weight_scales():
     if t is None or t.data_ptr() != (ptr.value or 0):
         raise RuntimeError(
             f"weight scales at {ptr.value or 0:#x} (granularity {gran.value}) "
-            f"were attached through fm_set_weight_scales directly, not through "
-            f"set_weight_scales: there is no tensor to return")
+            f"were attached through fm_set_weight_scales / "
+            f"fm_set_weight_block_scales directly, not through this module: "
+            f"there is no tensor to return")
     return t
 
 
@@ -276,6 +334,55 @@ def pack_weight_scales(up, down, glu=None):
     H = agreed("H", [parts[1].size(1)], cfg["hidden_size"] if cfg else None)
     dev = next((t.device for t in parts if t.size(1) != 1), parts[0].device)
     cols = [t.to(dev).expand(nE, w) for t, w in zip(parts, (P, H, P))]
+    return torch.cat(cols, dim=1).contiguous()
+
+
+def pack_weight_block_scales(up, down, glu=None):
+    """Build the [nE, BSC] block-scale tensor from per-matrix grids: `up`
+    [nE, PB, HB] (Wup [P, H]), `down` [nE, HB, PB] (the down buffer used as
+    [H, P]) and, for gated experts, `glu` [nE, PB, HB], with PB = P / 128 and
+    HB = H / 128; each grid is [output block, K block]. nE counts the shared
+    experts, which come last. A 0-dim or [nE] tensor is a per-tensor scale
+    and spreads over the grid (a 0-dim one over the experts too). nE, PB and
+    HB come from the 3-D arguments, else from the initialized config. Returns
+    a contiguous float32 tensor on the device of the first 3-D argument, with
+    records [s_up | s_dn | s_glu]."""
+    import torch
+
+    named = [("up", up), ("down", down)] + ([("glu", glu)] if glu is not None
+                                            else [])
+    parts = [(n, torch.as_tensor(t, dtype=torch.float32)) for n, t in named]
+    for name, t in parts:
+        if t.dim() not in (0, 1, 3):
+            raise ValueError(
+                f"{name} block scales must be 0-dim, [nE] or [nE, output "
+                f"blocks, K blocks]; got {list(t.shape)}")
+    cfg = _state["cfg"]
+    # (nE, PB, HB) as each 3-D argument sees them; down is [nE, HB, PB]
+    seen = {(t.size(0), t.size(2), t.size(1)) if name == "down"
+            else tuple(t.shape) for name, t in parts if t.dim() == 3}
+    seen_ne = {t.size(0) for _, t in parts if t.dim() == 1}
+    if len(seen) > 1 or len(seen_ne | {d[0] for d in seen}) > 1:
+        raise ValueError(
+            f"pack_weight_block_scales: the arguments disagree on "
+            f"(nE, P/128, H/128): {sorted(seen)}"
+            + (f" and nE {sorted(seen_ne)}" if seen_ne else ""))
+    if seen:
+        nE, PB, HB = next(iter(seen))
+    elif cfg:
+        PB, HB = cfg["intermediate_size"] // 128, cfg["hidden_size"] // 128
+        nE = next(iter(seen_ne), _weight_block_scale_shape()[0])
+    else:
+        raise ValueError(
+            "pack_weight_block_scales cannot infer the grid from per-tensor "
+            "arguments alone: pass a 3-D tensor, or call after initialize()")
+    dev = next((t.device for _, t in parts if t.dim() == 3), parts[0][1].device)
+    cols = []
+    for name, t in parts:
+        shape = (nE, HB, PB) if name == "down" else (nE, PB, HB)
+        if t.dim() == 1:
+            t = t.reshape(-1, 1, 1)
+        cols.append(t.to(dev).expand(shape).reshape(nE, PB * HB))
     return torch.cat(cols, dim=1).contiguous()
 
 
@@ -383,7 +490,8 @@ def _validate_forward_args(input, gate_weights, expert_weights):
     return S, H, E, P, nLx
 
 
-def moe_forward(input, gate_weights, expert_weights, weight_scales=None):
+def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
+                weight_block_scales=None):
     """Mirror of _C.moe_forward (python_bindings.cu:17-151): one DMoE
     forward on this rank's tokens. Single-rank path; world>1 uses the EP
     pipeline in ep.py (same result per rank). With
@@ -391,12 +499,19 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None):
     (shared slabs last) and every token also receives the unscaled sum of
     the shared FFNs. weight_scales (torch_dtype 4 / 5): a
     tensor as for set_weight_scales; one that is not the attached tensor is
-    attached first, None leaves the attachment as it is."""
+    attached first, None leaves the attachment as it is. weight_block_scales
+    (torch_dtype 4): the same for set_weight_block_scales; pass one kind."""
     import torch
 
     S, H, E, P, nLx = _validate_forward_args(input, gate_weights, expert_weights)
     if weight_scales is not None and weight_scales is not _state["weight_scales"]:
         set_weight_scales(weight_scales)
+    if weight_block_scales is not None:
+        if weight_scales is not None:
+            raise ValueError("pass weight_scales or weight_block_scales, not "
+                             "both: one kind of scale is attached at a time")
+        if weight_block_scales is not _state["weight_scales"]:
+            set_weight_block_scales(weight_block_scales)
     if _state["world"] != 1:
         from . import ep
 

@@ -187,7 +187,8 @@ int fm_get_router(fm_router_config* out);
  * order - and the shared experts' records trail the routed ones. Every value
  * must be finite; the contents are not checked.
  * granularity: 0 none (scales ignored, may be NULL), 1 per output channel,
- * 2 reserved for 128x128 blocks -> FM_ERR_UNSUPPORTED.
+ * 2 (128x128 blocks) -> FM_ERR_UNSUPPORTED here: this record cannot describe
+ * blocks, fm_set_weight_block_scales below attaches them.
  * Valid after fm_initialize; fm_initialize and fm_finalize reset to none.
  * The tensor is BORROWED until the next fm_set_weight_scales / fm_finalize;
  * the caller may rewrite its contents in place between forwards. A set call
@@ -200,6 +201,36 @@ int fm_get_router(fm_router_config* out);
  * torch_dtype other than 4 or 5; granularity 2. */
 int fm_set_weight_scales(const float* scales, int32_t granularity);
 int fm_get_weight_scales(const float** scales, int32_t* granularity);
+
+/* 128x128 block scales of the fp8 expert weights (dtype 4 only; DESIGN.md
+ * par.5m): the layout of the official FP8 releases of DeepSeek-V3 / R1 and
+ * Qwen3-MoE. Every expert weight matrix W [R, C] (R output channels, C = K)
+ * has an fp32 grid s [R/128, C/128]:
+ *   W_eff[r, c] = float(W_fp8[r, c]) * s[r / 128][c / 128]
+ * The product is formed by accumulator promotion: the MFMA sums a K block of
+ * 128 with the exactly dequantised weights, and one fp32 FMA per accumulator
+ * element adds s times that sum. Bias, activation, gating and the combine are
+ * unchanged.
+ * scales: device fp32, contiguous [nLx + nSh, BSC]; with PB = P/128 and
+ * HB = H/128, BSC = 2*PB*HB (3*PB*HB when gated). An expert's record is
+ * [s_up (PB x HB) | s_dn (HB x PB) | s_glu (PB x HB)] - the slab order, each
+ * part row-major as [output block, K block] - and the shared experts' records
+ * trail the routed ones. Every value must be finite; the contents are not
+ * checked. NULL detaches.
+ * Lifetime as fm_set_weight_scales: BORROWED until the next set call of either
+ * kind or fm_finalize, rewritable in place between forwards, reset by
+ * fm_initialize / fm_finalize, and a set call invalidates the captured forward
+ * graph. One kind of scale is attached at a time: either set call detaches
+ * the other kind. While block scales are attached fm_get_weight_scales
+ * reports granularity 2 and this pointer.
+ * Read by the same entry points as the per-channel scales, at S >= 128 and at
+ * decode sizes; such a forward always runs the multi-kernel path. The grouped
+ * GEMMs then run the 256x128, 128x256 or 128x128 tile (the 256x256 tile and
+ * the small synchronous kernel have no block-scale variant; FM_FORCE_MODE 0
+ * and 2 are mapped like the default choice).
+ * FM_ERR_UNSUPPORTED (the message names the cause): a torch_dtype other than
+ * 4; hidden_size or intermediate_size not a multiple of 128. */
+int fm_set_weight_block_scales(const float* scales);
 
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */

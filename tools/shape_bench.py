@@ -2,7 +2,7 @@
 
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
                                    [--router qwen|v2|v3|sigmoid]
-                                   [--weight-scales]
+                                   [--weight-scales | --weight-block-scales]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -28,7 +28,9 @@ counted once, and floor_us = weight_bytes /
 runs of `steps` forwards under FM_DECODE_FFN=1 and R under =0, alternated,
 and reports every run. --weight-scales (dtype 4 and 5 only, DESIGN.md
 par.5l) attaches a random per-output-channel weight-scale tensor,
-exp2(U(-2, 1)) per channel.
+exp2(U(-2, 1)) per channel. --weight-block-scales (dtype 4 only, DESIGN.md
+par.5m; H and P multiples of 128) attaches one such scale per 128x128 weight
+block instead.
 """
 import ctypes
 import json
@@ -77,6 +79,9 @@ if mini_batch_form:
 weight_scales = "--weight-scales" in argv
 if weight_scales:
     argv.remove("--weight-scales")
+weight_block_scales = "--weight-block-scales" in argv
+if weight_block_scales:
+    argv.remove("--weight-block-scales")
 ab_runs = 0
 if "--decode-ab" in argv:
     i = argv.index("--decode-ab")
@@ -97,6 +102,9 @@ from flashmoe_amd.config import expert_mats, torch_dtype_of, weight_dtype_of
 if weight_scales and dtype_code not in (4, 5):
     sys.exit("--weight-scales needs fp8 expert weights: dtype 4 or 5")
 
+if weight_block_scales and (dtype_code != 4 or weight_scales):
+    sys.exit("--weight-block-scales needs dtype 4 and excludes --weight-scales")
+
 adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
 x_first = torch.randn(1, s_list[0], H, dtype=adt, device="cuda")
@@ -115,6 +123,12 @@ if weight_scales:
     # without the flag
     w_scales = torch.exp2(3.0 * torch.rand(
         E + n_shared, P + H + (P if expert_mats(hidden_act) == 3 else 0),
+        dtype=torch.float32, device="cuda",
+        generator=torch.Generator(device="cuda").manual_seed(48)) - 2.0)
+if weight_block_scales:
+    # one scale per 128x128 block, 2^[-2, 1) like the per-channel arm
+    w_scales = torch.exp2(3.0 * torch.rand(
+        E + n_shared, expert_mats(hidden_act) * (P // 128) * (H // 128),
         dtype=torch.float32, device="cuda",
         generator=torch.Generator(device="cuda").manual_seed(48)) - 2.0)
 lib = _ext.load()
@@ -140,7 +154,9 @@ def measure(S):
     os.unlink(f.name)
     if score_bias is not None:
         moe.set_score_bias(score_bias)
-    if w_scales is not None:
+    if weight_block_scales:
+        moe.set_weight_block_scales(w_scales)
+    elif w_scales is not None:
         moe.set_weight_scales(w_scales)
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
@@ -224,7 +240,8 @@ def measure(S):
                      + (f" shared={n_shared}" if n_shared else "")
                      + (f" compose={n_compose}" if n_compose else "")
                      + (f" router={router}" if router else "")
-                     + (" weight-scales" if weight_scales else "")),
+                     + (" weight-scales" if weight_scales else "")
+                     + (" weight-block-scales" if weight_block_scales else "")),
         "us_per_fwd": round(dt * 1e6, 1),
         "tokens_per_s": round(S / dt),
         "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
