@@ -3,6 +3,7 @@ implementation (flashmoe_amd). Mirrors the reference package surface
 (flashmoe/__init__.py: run_moe, get_compiled_config)."""
 from flashmoe_amd import (  # noqa: F401
     finalize,
+    get_activation_quant,
     get_compiled_config,
     get_num_local_experts,
     get_router,
@@ -12,6 +13,7 @@ from flashmoe_amd import (  # noqa: F401
     pack_weight_block_scales,
     pack_weight_scales,
     run_moe,
+    set_activation_quant,
     set_score_bias,
     set_weight_block_scales,
     set_weight_scales,

@@ -6,6 +6,7 @@ Drop-in surface mirroring the reference package `flashmoe`
 """
 from .moe import (  # noqa: F401
     finalize,
+    get_activation_quant,
     get_compiled_config,
     get_num_local_experts,
     get_num_shared_experts,
@@ -15,6 +16,7 @@ from .moe import (  # noqa: F401
     moe_forward,
     pack_weight_block_scales,
     pack_weight_scales,
+    set_activation_quant,
     set_score_bias,
     set_weight_block_scales,
     set_weight_scales,
@@ -37,4 +39,6 @@ __all__ = [
     "pack_weight_scales",
     "set_weight_block_scales",
     "pack_weight_block_scales",
+    "set_activation_quant",
+    "get_activation_quant",
 ]

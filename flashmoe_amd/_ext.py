@@ -65,6 +65,12 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_set_weight_scales.restype = ctypes.c_int
     lib.fm_set_weight_block_scales.argtypes = [p]
     lib.fm_set_weight_block_scales.restype = ctypes.c_int
+    lib.fm_set_activation_quant.argtypes = [ctypes.c_int]
+    lib.fm_set_activation_quant.restype = ctypes.c_int
+    lib.fm_get_activation_quant.argtypes = []
+    lib.fm_get_activation_quant.restype = ctypes.c_int
+    lib.fm_quant_fp8_g128.argtypes = [p, p, p, p, i64, i64]
+    lib.fm_quant_fp8_g128.restype = ctypes.c_int
     lib.fm_get_weight_scales.argtypes = [ctypes.POINTER(p),
                                          ctypes.POINTER(ctypes.c_int32)]
     lib.fm_get_weight_scales.restype = ctypes.c_int

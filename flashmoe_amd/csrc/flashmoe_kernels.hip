@@ -67,6 +67,7 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
   else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   else if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
   else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else if constexpr (N == 7) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
   else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
   else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
   else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
@@ -2751,6 +2752,478 @@ __global__ __launch_bounds__(512, 2) void k_group_gemm_mx(GemmArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// fp8 activations for dtype 4 (fm_set_activation_quant(1))
+//
+// Quantiser. A bf16 row is cut into groups of 128 along K; per group
+//   amax = max|v|, s = amax / 448 (1.0 for a zero group), q = e4m3_rne(v / s)
+// with both divisions IEEE fp32. Output: the e4m3 bytes laid out like the
+// input ([rows, K] bytes) and the scales as fp32 [rows, K/128] row-major with
+// a row pitch of sPitch floats (K/128 for fm_quant_fp8_g128; the library's
+// own workspaces round it up to a multiple of 4, aq_scale_pitch, so that a
+// row's scales can be fetched 16 bytes at a time).
+// One group per 8 lanes: a lane owns 16 consecutive elements (two 16-byte
+// loads, one 16-byte store), the group amax is three xor-shuffles. The loop
+// trip count is block-uniform; lanes past the last group re-read it and
+// store nothing, so exactly `rows` rows are touched.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) FM_NO_PK_F32
+void k_quant_fp8_g128(const bf16* __restrict__ in, uint8_t* __restrict__ out8,
+                      float* __restrict__ scales, long long rows, int K,
+                      int sPitch) {
+  const int KB = K / 128;
+  const long long nGrp = rows * KB;
+  const int sub = threadIdx.x & 7;
+  for (long long base = (long long)blockIdx.x * 32; base < nGrp;
+       base += (long long)gridDim.x * 32) {
+    const long long gi = base + (threadIdx.x >> 3);
+    const long long gc = gi < nGrp ? gi : nGrp - 1;
+    const u32x4* src =
+        reinterpret_cast<const u32x4*>(in + gc * 128 + sub * 16);
+    const u32x4 w0 = src[0], w1 = src[1];
+    float v[16];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      v[2 * d] = __uint_as_float(w0[d] << 16);
+      v[2 * d + 1] = __uint_as_float(w0[d] & 0xFFFF0000u);
+      v[8 + 2 * d] = __uint_as_float(w1[d] << 16);
+      v[8 + 2 * d + 1] = __uint_as_float(w1[d] & 0xFFFF0000u);
+    }
+    float m = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m = fmaxf(m, fabsf(v[i]));
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1)
+      m = fmaxf(m, __shfl_xor(m, off, 8));
+    const float s = m > 0.0f ? m / 448.0f : 1.0f;
+    u32x4 q;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      float c[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)  // saturate: v / s may round a hair past 448
+        c[i] = fminf(fmaxf(v[4 * d + i] / s, -448.0f), 448.0f);
+      uint32_t pk = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0u, false);
+      pk = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], pk, true);
+      q[d] = pk;
+    }
+    if (gi < nGrp) {
+      *reinterpret_cast<u32x4*>(out8 + gi * 128 + sub * 16) = q;
+      if (sub == 0) scales[(gi / KB) * sPitch + gi % KB] = s;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Grouped GEMM, e4m3 activations x e4m3 weights (par.5n). Per K block kb of
+// 128 the fp8 MFMA (v_mfma_scale_f32_16x16x128_f8f6f4, both hardware scales
+// 1.0, ZERO C operand) gives the block's exact-product fp32 sum `part`; it is
+// folded at once: acc = fma(part, sA[row, kb] * sW[n / 128, kb], acc). So the
+// block-scale promotion needs no second accumulator set across tiles.
+//
+// Staging is mx_gemm_job_body's: 128-byte rows, XOR-16B-chunk swizzle,
+// global_load_lds, BK = 128, 512 threads = 2M x 4N waves, BM = 128. BN = 128
+// double-buffers (64 KiB, two blocks per CU); BN = 256 triple-buffers with
+// counted vmcnt waits (144 KiB, one block per CU).
+//
+// The MFMA operands are SWAPPED (weight fragment first), which is free here
+// because both hardware scales are 1.0: the accumulator then holds C^T, lane
+// & 15 is the output ROW of fragment mi and 4 * (lane >> 4) + r are four
+// consecutive output COLUMNS. Hence sA is ONE value per (lane, mi, K block)
+// instead of four, and the epilogue stores 8 bytes per (mi, ni).
+//
+// sA: fp32 [rows, K/128] as k_quant_fp8_g128 writes it. It is staged into
+// LDS beside the A tile by the same pipeline (one more 4-byte
+// global_load_lds per wave and stage, rows gathered like the A rows), so a
+// tile's BM scales land with the tile, one or two tiles ahead of their use,
+// and every wave's counted vmcnt wait is GPW_AB + 1 per stage in flight.
+// sW: wave-uniform per K block (a wave spans <= 64 columns inside one 128
+// block), scalar loads one block ahead as in par.5m; two values in the gated
+// up phase. a.bScale == nullptr means 1.0, so no-scale, per-channel and
+// block-scaled weights share one instantiation. A per-channel scale stays in
+// the epilogue.
+//
+// GATED (PHASE 0, effective N = 2P, BN = 256): the B tile's even 16-row
+// fragments are Wglu rows and the odd ones Wup rows of the same P columns
+// (par.5f), a.gluOffset apart, so accv[mi][2j] / accv[mi][2j+1] are g / u of
+// one output element and the tile is 128 rows x 128 P-columns.
+// PHASE semantics (0 up / 1 down + combine slots / 2 packed rows), shared
+// expert slices, bias and per-channel scales follow gemm_job_body. act and
+// the bias pointer are run-time, wave-uniform arguments.
+// ---------------------------------------------------------------------------
+// row pitch, in floats, of the activation-scale workspaces
+__host__ __device__ constexpr int aq_scale_pitch(int KB) { return (KB + 3) & ~3; }
+
+template <int BN> __host__ __device__ constexpr int aq_stages() {
+  return BN == 256 ? 3 : 2;
+}
+template <int BN> __host__ __device__ constexpr int aq_lds_bytes() {
+  return aq_stages<BN>() * ((128 + BN) * 128 + 8 * 64 * 4) + 128 * 8 +
+         128 * 4 + 16;
+}
+
+template <int PHASE, bool GATED, int BN>
+__device__ __forceinline__ void aq_gemm_job_body(const GemmArgs& a,
+                                                 char* smemBase, int e, int m0,
+                                                 int n0) {
+  static_assert(!GATED || (PHASE == 0 && BN == 256),
+                "gated: up phase, 128 P-columns per tile");
+  constexpr int BM = 128, BK = 128;
+  constexpr int SE = aq_stages<BN>();
+  uint8_t* Abase = reinterpret_cast<uint8_t*>(smemBase);   // SE x [BM][BK]
+  uint8_t* Bbase = reinterpret_cast<uint8_t*>(smemBase + SE * BM * BK);
+  TPS* sTps = reinterpret_cast<TPS*>(smemBase + SE * (BM + BN) * BK);
+  float* sScale = reinterpret_cast<float*>(sTps + BM);     // [BM] row scales
+  uint32_t* sRouted = reinterpret_cast<uint32_t*>(sScale + BM);
+  float* sSA = reinterpret_cast<float*>(sRouted + 4);  // SE x [8 waves][64]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int K = a.K, N = a.N;
+  const int KB = K / BK;
+
+  const TPS* tpsE = a.tokenIds ? a.tokenIds + (size_t)e * a.pEC : nullptr;
+  __syncthreads();  // prior job's LDS readers done
+  if (tid == 0)
+    *sRouted = tpsE ? min(a.eC[e], (uint32_t)a.EC) : (uint32_t)a.nRows;
+  __syncthreads();
+  const uint32_t routed = *sRouted;
+  if ((uint32_t)m0 >= routed) return;
+  const int mCap = a.tokenIds ? a.pEC : a.nRows;
+  const int we = a.segExpert ? a.segExpert[e] : e;
+  // slot / scaled / nSlot: as in gemm_job_body (a shared-expert slice,
+  // e >= nRoutedE, is unscaled and reads no gate_out column)
+  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
+  if (tid < BM) {
+    TPS t{0u, 1.0f};
+    if ((uint32_t)(m0 + tid) < routed)
+      t = tpsE ? tpsE[m0 + tid] : TPS{(uint32_t)(m0 + tid), 1.0f};
+    sTps[tid] = t;
+    if constexpr (PHASE == 1) {
+      float sc = 1.0f;
+      if (scaled && (uint32_t)(m0 + tid) < routed)
+        sc = toF(reinterpret_cast<const bf16*>(
+                 a.gate_out)[(size_t)tpsTok(t.tokenIdx) * a.PX +
+                             a.expertOffset + e]) / t.probSum;
+      sScale[tid] = sc;
+    }
+  }
+  __syncthreads();
+
+  const uint8_t* __restrict__ Ag = reinterpret_cast<const uint8_t*>(a.A);
+  const uint8_t* __restrict__ Bg =
+      reinterpret_cast<const uint8_t*>(a.B) + (size_t)we * a.strideBExpert;
+  const float* __restrict__ aS = reinterpret_cast<const float*>(a.aScales);
+
+  // staging geometry of mx_gemm_job_body: 1 KiB groups of 8 rows x 128 B
+  const int grow8 = lane >> 3;
+  const int schunk = (lane & 7) ^ grow8;
+  constexpr int GPW_A = BM / 8 / 8;
+  constexpr int GPW_B = BN / 8 / 8;
+  constexpr int GPW_AB = GPW_A + GPW_B;
+  const size_t aBase = (size_t)e * a.strideAExpert;  // bytes; a multiple of K
+  auto aRowOf = [&](int row) -> size_t {
+    return (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
+                        : (size_t)min(m0 + row, mCap - 1);
+  };
+  const uint8_t* aSrc[GPW_A];
+  const uint8_t* bSrc[GPW_B];
+#pragma unroll
+  for (int i = 0; i < GPW_A; ++i) {
+    const int row = (wave * GPW_A + i) * 8 + grow8;
+    aSrc[i] = Ag + aBase + aRowOf(row) * (size_t)K + schunk * 16;
+  }
+#pragma unroll
+  for (int i = 0; i < GPW_B; ++i) {
+    const int row = (wave * GPW_B + i) * 8 + grow8;
+    if constexpr (GATED) {
+      const int f = row >> 4;
+      const int prow =
+          min((n0 >> 1) + (f >> 1) * 16 + (row & 15), (N >> 1) - 1);
+      bSrc[i] = Bg + ((f & 1) ? 0 : a.gluOffset) + (size_t)prow * K +
+                schunk * 16;
+    } else {
+      bSrc[i] = Bg + (size_t)min(n0 + row, N - 1) * K + schunk * 16;
+    }
+  }
+  // sA rides the same pipeline: per stage the first 16 lanes of every wave
+  // DMA the aligned quad of scales [4 * (kb / 4), +4) of the wave's 16 A rows
+  // (wave * 16 + lane) into sSA[buf][wave][lane][0..3], one 16-byte
+  // global_load_lds (rows are aq_scale_pitch floats apart, a multiple of 4).
+  // All eight waves so issue the same GPW_AB + 1 loads per stage and one
+  // counted wait serves them all. No register-returning VMEM load is left in
+  // the K loop, and no 4-byte LDS DMA either (the compiler orders every LDS
+  // read behind those with a vmcnt(0) of its own).
+  const float* saSrc = aS + (aBase / (size_t)K + aRowOf(wave * 16 + (lane & 15))) *
+                                (size_t)aq_scale_pitch(KB);
+  auto stage = [&](int kb, int buf) {
+    const int kt = kb * BK;
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(aSrc[i] + kt),
+          (las_u32*)(Abase + buf * BM * BK + (wave * GPW_A + i) * 1024), 16,
+          0, 0);
+#pragma unroll
+    for (int i = 0; i < GPW_B; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(bSrc[i] + kt),
+          (las_u32*)(Bbase + buf * BN * BK + (wave * GPW_B + i) * 1024), 16,
+          0, 0);
+    if (lane < 16)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(saSrc + (kb & ~3)),
+          (las_u32*)(sSA + buf * 512 + wave * 64), 16, 0, 0);
+  };
+  constexpr int GPS = GPW_AB + 1;  // loads per wave and stage
+
+  const int wr = wave >> 2, wc = wave & 3;
+  constexpr int MI = BM / 32, NF = BN / 64;
+  f32x4 accv[MI][NF];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) accv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int rl = lane & 15;
+  const int gk = lane >> 4;
+  // sA of this lane in a stage: fragment mi's row rl (swapped operands) was
+  // staged by wave wr * 4 + mi, lane rl, as four floats
+  const int saOff = wr * 4 * 64 + rl * 4;
+  // sW row(s) of this wave: block row of its first column (clamped like the
+  // B rows of a wave wholly past N)
+  cas_f32* bsRow = nullptr;
+  float sw = 1.0f, swG = 1.0f, swNext = 1.0f, swGNext = 1.0f;
+  if (a.bScale) {
+    const int nCol = GATED ? min((n0 >> 1) + wc * (BN / 8), (N >> 1) - 1)
+                           : min(n0 + wc * (BN / 4), N - 1);
+    const int row =
+        __builtin_amdgcn_readfirstlane((nCol >> 7) * a.bScaleKB);
+    bsRow = (cas_f32*)(a.bScale + (size_t)we * a.bScaleStride) + row;
+    sw = bsRow[0];
+    if constexpr (GATED) swG = bsRow[a.bScaleGlu];
+  }
+
+  const int nK = KB;
+  stage(0, 0);
+  if constexpr (SE == 3) {
+    if (nK > 1) {
+      stage(1, 1);
+      wait_vmcnt<GPS>();  // tile 0 landed; tile 1 in flight
+    } else {
+      wait_vmcnt<0>();
+    }
+  } else {
+    wait_vmcnt<0>();
+  }
+  __builtin_amdgcn_s_barrier();
+  const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < nK; ++t) {
+    const int pre = t + SE - 1;      // tile staged this iteration
+    const bool stageNow = pre < nK;
+    if (t + 1 < nK && bsRow) {  // next block's sW (scalar loads)
+      swNext = bsRow[t + 1];
+      if constexpr (GATED) swGNext = bsRow[a.bScaleGlu + t + 1];
+    }
+    const uint8_t* Al = Abase + (t % SE) * BM * BK;
+    const uint8_t* Bl = Bbase + (t % SE) * BN * BK;
+    const float* sAl = sSA + (t % SE) * 512 + saOff + (t & 3);
+    __builtin_amdgcn_s_setprio(1);
+    i32x8 af[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const int R = wr * (BM / 2) + mi * 16 + rl;
+      const int c0 = (2 * gk) ^ (R & 7);
+      const int c1 = (2 * gk + 1) ^ (R & 7);
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(&Al[R * BK + c0 * 16]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(&Al[R * BK + c1 * 16]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        af[mi][d] = (int)lo[d];
+        af[mi][4 + d] = (int)hi[d];
+      }
+    }
+    i32x8 bfr[NF];
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni) {
+      const int R = wc * (BN / 4) + ni * 16 + rl;
+      const int c0 = (2 * gk) ^ (R & 7);
+      const int c1 = (2 * gk + 1) ^ (R & 7);
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(&Bl[R * BK + c0 * 16]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(&Bl[R * BK + c1 * 16]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        bfr[ni][d] = (int)lo[d];
+        bfr[ni][4 + d] = (int)hi[d];
+      }
+    }
+    float sm[MI], smG[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const float sa = sAl[mi * 64];
+      sm[mi] = sa * sw;
+      smG[mi] = GATED ? sa * swG : sm[mi];
+    }
+    // The tile's fragments are read BEFORE the next stage is issued: the
+    // compiler puts a vmcnt(0) of its own in front of these LDS reads (seen
+    // in the ISA, whatever the source order of the MFMAs), and here it only
+    // finds the tile staged one iteration ago, which had a whole compute
+    // phase to land, instead of draining the loads just issued.
+    if (stageNow) stage(pre, pre % SE);
+    // The MFMAs of fragment column ni + 1 are written ahead of the fold of
+    // column ni (two part[] sets) so that the fold's FMAs can run under the
+    // MFMA pipe's shadow (the compiler keeps two MFMAs in flight).
+    f32x4 part[2][MI];
+    auto issue = [&](int ni) __attribute__((always_inline)) {
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+        part[ni & 1][mi] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            bfr[ni], af[mi], zero4, 0 /*fp8*/, 0 /*fp8*/, 0, 0x7F, 0, 0x7F);
+    };
+    issue(0);
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni) {
+      if (ni + 1 < NF) issue(ni + 1);
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) {
+        const float s = (GATED && (ni & 1) == 0) ? smG[mi] : sm[mi];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          accv[mi][ni][r] = fmaf(part[ni & 1][mi][r], s, accv[mi][ni][r]);
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+    sw = swNext;
+    swG = swGNext;
+    if constexpr (SE == 3) {
+      if (stageNow) wait_vmcnt<GPS>(); else wait_vmcnt<0>();
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+  }
+
+  // epilogue: lane & 15 is the row of fragment mi, accv[mi][ni][0..3] are
+  // columns cq..cq+3 of fragment ni. Reads sTps / sScale only: the stage
+  // buffers are free for the next job's prologue.
+  const int cq = gk * 4;
+  const int act = a.act;
+  const int nOut = GATED ? (N >> 1) : N;  // output columns (and row pitch)
+  constexpr int NOUT = GATED ? NF / 2 : NF;
+  const int oBase =
+      (GATED ? (n0 >> 1) + wc * (BN / 8) : n0 + wc * (BN / 4)) + cq;
+  float bv[NOUT][4], sv[NF][4];
+#pragma unroll
+  for (int no = 0; no < NOUT; ++no)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[no][r] = 0.f;
+  if (a.bias) {
+    const bf16* bptr = reinterpret_cast<const bf16*>(a.bias) +
+                       (a.strideBExpert ? (size_t)we * nOut : 0);
+#pragma unroll
+    for (int no = 0; no < NOUT; ++no)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = oBase + no * 16 + r;
+        if (col < nOut) bv[no][r] = toF(bptr[col]);
+      }
+  }
+  {
+    const float* sp =
+        a.wScale ? a.wScale + (size_t)we * a.wScaleStride : nullptr;
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (GATED)
+          sv[ni][r] = wscale_at(
+              sp ? sp + ((ni & 1) ? 0 : a.wScaleGlu) : nullptr,
+              oBase + (ni >> 1) * 16 + r, nOut);
+        else
+          sv[ni][r] = wscale_at(sp, oBase + ni * 16 + r, nOut);
+      }
+  }
+  bf16* outBase;
+  if constexpr (PHASE == 1)
+    outBase = reinterpret_cast<bf16*>(slot ? (void*)a.O32 : a.moe_out);
+  else
+    outBase = reinterpret_cast<bf16*>(a.out) + (size_t)e * a.strideOExpert;
+  const long long rowPitch = (PHASE == 1) ? a.H : nOut;
+  const bool vecOK = (rowPitch & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(outBase) & 7) == 0;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int row = wr * (BM / 2) + mi * 16 + rl;
+    const int m = m0 + row;
+    if ((uint32_t)m >= routed) continue;  // rows past routed: not written
+    bf16* orow;
+    float rowScale = 1.0f;
+    if constexpr (PHASE == 1) {
+      const TPS tp = sTps[row];
+      if (slot) {
+        orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
+                          tpsJ(tp.tokenIdx)) * rowPitch;
+        rowScale = sScale[row];
+      } else {
+        orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+      }
+    } else {
+      orow = outBase + (size_t)m * rowPitch;
+    }
+#pragma unroll
+    for (int no = 0; no < NOUT; ++no) {
+      const int col0 = oBase + no * 16;
+      const int nValid = nOut - col0;
+      if (nValid <= 0) continue;  // columns >= N are not written
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (GATED) {
+          v[r] = gate_act(accv[mi][2 * no][r] * sv[2 * no][r], act) *
+                 (accv[mi][2 * no + 1][r] * sv[2 * no + 1][r]);
+        } else {
+          v[r] = accv[mi][no][r] * sv[no][r] + bv[no][r];
+          if constexpr (PHASE == 0)
+            v[r] = (act == 0)
+                ? fmaxf(v[r], 0.0f)
+                : 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752f));
+          if constexpr (PHASE == 1)
+            if (slot) v[r] = v[r] * rowScale;
+        }
+      }
+      storeRow4<false>(orow + col0, v, nValid, vecOK);
+    }
+  }
+}
+
+template <int PHASE, bool GATED, int BN>
+__global__ __launch_bounds__(512, BN == 256 ? 1 : 2) FM_NO_PK_F32
+void k_group_gemm_aq(GemmArgs a) {
+  constexpr int BM = 128;
+  __shared__ __attribute__((aligned(16))) char smem[aq_lds_bytes<BN>()];
+  const int mT = a.totalJobs > 0 ? a.jobsMT : gridDim.x;
+  const int nT = a.totalJobs > 0 ? a.jobsNT : gridDim.y;
+  const int gstride = gridDim.x * gridDim.y * gridDim.z;
+  const int nBlocks = a.totalJobs > 0 ? a.totalJobs : gstride;
+  const int lin0 =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int qx = nBlocks / 8, rx = nBlocks % 8;
+  for (int jl = lin0; jl < nBlocks; jl += gstride) {
+    const int xcd = jl % 8, pos = jl / 8;
+    const int swz = a.noRemap
+        ? jl
+        : (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+    const int e = swz / (mT * nT);
+    const int rem = swz % (mT * nT);
+    aq_gemm_job_body<PHASE, GATED, BN>(a, smem, e, (rem % mT) * BM,
+                                       (rem / mT) * BN);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fp32 grouped GEMM (config-1 "CPU correctness plumbing" shapes; VALU
 // tiled). 64x64 tile, 256 threads, each thread a 4x4 sub-block, BK=16.
 // Same phase semantics as the bf16 kernel.
@@ -4078,6 +4551,9 @@ __global__ __launch_bounds__(512, 1) void k_moe_fused(GemmArgs gl, GemmArgs gu,
 
 static int launch_group_gemm(hipStream_t st, int phase, const struct GemmArgs& a,
                              int M, int nE);
+static int launch_quant_g128(hipStream_t st, const void* in, uint8_t* out,
+                             uint8_t* scales, long long nRows, int K,
+                             int sPitch = 0);
 
 namespace {
 
@@ -4132,6 +4608,9 @@ struct State {
   uint8_t* xs = nullptr;     // dtype 5: x block scales [S, H/64]
   uint8_t* xM8 = nullptr;    // dtype 5: quantized intermediates
   uint8_t* xMs = nullptr;    // dtype 5: xM block scales
+  // (dtype 4 with fm_set_activation_quant(1), DESIGN.md par.5n: the same four,
+  // allocated by the set call; xs / xMs then hold fp32 [rows, K/128])
+  int actQuant = 0;          // 0 off, 1 group128; part of the graph key
   float* O32 = nullptr;      // [S, H] (staged-API combine accumulator)
   void* cbuf = nullptr;      // [S, k, H] Element: non-atomic combine slots
   uint8_t* kept = nullptr;   // [S, k] capacity-kept mask (gate-written)
@@ -4740,6 +5219,7 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   g.wScale = nullptr;  // and without weight scales
   g.bScale = nullptr;
   g.wScaleGran = 0;
+  g.actQuant = 0;  // and with bf16 activations
   g.cfg = *cfg;
   g.rank = rank;
   g.world = world_size;
@@ -5142,6 +5622,77 @@ int fm_set_weight_block_scales(const float* scales) {
   g.wScaleGran = scales ? 2 : 0;
   ++g.wScaleGen;  // never replay a forward captured under other scales
   return FM_OK;
+}
+
+int fm_set_activation_quant(int mode) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (mode != 0 && mode != 1) {
+    snprintf(g_err, sizeof(g_err),
+             "activation quant mode must be 0 (off) or 1 (group128); got %d",
+             mode);
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (mode == 1) {
+    if (g.cfg.dtype != 4) {
+      snprintf(g_err, sizeof(g_err),
+               "activation quant group128 needs fp8 expert weights with bf16 "
+               "activations: torch_dtype must be 4, the config has torch_dtype "
+               "%d", (int)g.cfg.dtype);
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (g.H % 128 != 0 || g.P % 128 != 0) {
+      snprintf(g_err, sizeof(g_err),
+               "activation quant group128 needs hidden_size and "
+               "intermediate_size to be multiples of the 128 group; got "
+               "hidden_size %d, intermediate_size %d", g.H, g.P);
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (g.cfg.is_training) {
+      setErr("activation quant group128 is not supported with is_training 1 "
+             "(inference only)");
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (!g.x8) {
+      // here, outside any capture; sized like the dtype-5 workspaces for
+      // the forward (S rows) and the EP entry points (nLxAlloc * pEC rows)
+      const size_t qRows = std::max((size_t)g.S, (size_t)g.nLxAlloc * g.pEC);
+      uint8_t *a8 = nullptr, *as = nullptr, *m8 = nullptr, *ms = nullptr;
+      const bool ok =
+          hipMalloc(&a8, qRows * g.H) == hipSuccess &&
+          hipMalloc(&as, qRows * aq_scale_pitch(g.H / 128) * sizeof(float)) ==
+              hipSuccess &&
+          hipMalloc(&m8, (size_t)g.nLxAlloc * g.pEC * g.P) == hipSuccess &&
+          hipMalloc(&ms, (size_t)g.nLxAlloc * g.pEC *
+                             aq_scale_pitch(g.P / 128) * sizeof(float)) ==
+              hipSuccess;
+      if (!ok) {  // a refused call changes nothing
+        (void)hipFree(a8); (void)hipFree(as); (void)hipFree(m8);
+        (void)hipFree(ms);
+        (void)hipGetLastError();
+        setErr("activation quant: workspace allocation failed");
+        return FM_ERR_HIP;
+      }
+      g.x8 = a8; g.xs = as; g.xM8 = m8; g.xMs = ms;
+    }
+  }
+  g.actQuant = mode;
+  return FM_OK;
+}
+
+int fm_get_activation_quant(void) {
+  return g.initialized ? g.actQuant : -1;
+}
+
+int fm_quant_fp8_g128(void* stream, const void* in, void* out8, float* scales,
+                      int64_t rows, int64_t K) {
+  if (rows < 0 || K <= 0 || K % 128 != 0) {
+    setErr("fm_quant_fp8_g128: K must be a positive multiple of 128");
+    return FM_ERR_SHAPE;
+  }
+  return launch_quant_g128(reinterpret_cast<hipStream_t>(stream), in,
+                           reinterpret_cast<uint8_t*>(out8),
+                           reinterpret_cast<uint8_t*>(scales), rows, (int)K,
+                           (int)(K / 128));
 }
 
 int fm_get_weight_scales(const float** scales, int32_t* granularity) {
@@ -5650,6 +6201,75 @@ static int launch_quant_mx(hipStream_t st, const void* in, uint8_t* out,
   return FM_OK;
 }
 
+// fm_set_activation_quant(1): bf16 rows -> e4m3 + fp32 [rows, K/128] scales
+// (sPitch 0: the workspace pitch aq_scale_pitch that the GEMMs read)
+static int launch_quant_g128(hipStream_t st, const void* in, uint8_t* out,
+                             uint8_t* scales, long long nRows, int K,
+                             int sPitch) {
+  if (sPitch == 0) sPitch = aq_scale_pitch(K / 128);
+  const long long nGrp = nRows * (K / 128);
+  if (nGrp <= 0) return FM_OK;
+  const int grid = (int)std::min<long long>(DIVUP(nGrp, 32), 8192);
+  hipLaunchKernelGGL(k_quant_fp8_g128, dim3(grid), dim3(256), 0, st,
+                     reinterpret_cast<const bf16*>(in), out,
+                     reinterpret_cast<float*>(scales), nRows, K, sPitch);
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
+// fm_set_activation_quant(1): the e4m3 x e4m3 grouped GEMM (par.5n). The
+// caller describes the plain problem like launch_group_gemm's callers, with
+// a.A / a.aScales the quantised rows. Up phase: 128 output columns per tile
+// (ungated BN = 128; gated the effective BN = 256). Down / packed phase:
+// 128x256 where N affords it and the grid fills the chip, else 128x128.
+static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
+                                int M, int nE) {
+  const bool gated = phase == 0 && a.act >= 2;
+  if (gated && a.bias) {
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  GemmArgs aa = a;
+  aa.N = gated ? 2 * a.N : a.N;
+  aa.gluOffset = gated ? 2LL * a.N * a.K : 0;
+  aa.splitK = 1;
+  aa.noRemap = 0;
+  aa.totalJobs = 0;
+  const int nCU = g.nCU > 0 ? g.nCU : 256;
+  const bool wide =
+      gated || (phase != 0 && aa.N >= 256 &&
+                DIVUP(M, 128) * DIVUP(aa.N, 256) * nE >= nCU);
+  dim3 grid(DIVUP(M, 128), DIVUP(aa.N, wide ? 256 : 128), nE);
+  const int J = grid.x * grid.y * nE;
+  const int resident = (wide ? 1 : 2) * nCU;  // blocks per CU by LDS
+  if (J > resident) {
+    aa.totalJobs = J;
+    aa.jobsMT = grid.x;
+    aa.jobsNT = grid.y;
+    grid = dim3(resident, 1, 1);
+  }
+#define AQGG(PH)                                                              \
+  do {                                                                        \
+    if (wide)                                                                 \
+      hipLaunchKernelGGL((k_group_gemm_aq<PH, false, 256>), grid, dim3(512),  \
+                         0, st, aa);                                          \
+    else                                                                      \
+      hipLaunchKernelGGL((k_group_gemm_aq<PH, false, 128>), grid, dim3(512),  \
+                         0, st, aa);                                          \
+  } while (0)
+  if (gated)
+    hipLaunchKernelGGL((k_group_gemm_aq<0, true, 256>), grid, dim3(512), 0, st,
+                       aa);
+  else if (phase == 0)
+    hipLaunchKernelGGL((k_group_gemm_aq<0, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  else if (phase == 1) AQGG(1);
+  else AQGG(2);
+#undef AQGG
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
 static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
                             const void* expert_w, const void* b_up,
                             const void* b_dn, void* gate_out, void* moe_out,
@@ -5670,9 +6290,12 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // (nor does a decode-sized forward, S < 128: no ragged tile there)
   // (nor does a forward with weight scales attached: k_moe_fused is not
   // taught about them, its GemmArgs carry none)
+  // (nor does a forward with fp8 activations, fm_set_activation_quant(1):
+  // it runs the e4m3 x e4m3 GEMMs, whatever FM_FUSED says)
+  const bool aq = g.actQuant == 1;
   if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
       g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV &&
-      !g.wScale && !g.bScale) {
+      !g.wScale && !g.bScale && !aq) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
     if (rc != FM_FALLBACK) {
@@ -5702,9 +6325,13 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
     rc = launch_quant_mx(st, x, g.x8, g.xs, g.S, g.H);
     if (rc != FM_OK) return rc;
   }
+  if (aq) {  // group128: x once, after the gate (which read bf16 x)
+    rc = launch_quant_g128(st, x, g.x8, g.xs, g.S, g.H);
+    if (rc != FM_OK) return rc;
+  }
 
   GemmArgs up{};
-  up.A = (g.cfg.dtype == 5) ? (const void*)g.x8 : x;
+  up.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.x8 : x;
   up.aScales = g.xs;
   up.B = expert_w;
   up.bias = b_up;
@@ -5736,12 +6363,22 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
     up.outScales = g.xMs;  // (skips the separate k_quant_mx xM pass)
   }
   // decode-sized forward: the weight-streaming kernels (par.5k)
-  const bool decode = decodeFfnApplies();
+  // (never with fp8 activations, whatever FM_DECODE_FFN says: S < 128 runs
+  // the e4m3 x e4m3 GEMMs on the masked tile)
+  const bool decode = !aq && decodeFfnApplies();
   g.lastForwardDecodeFfn = decode;
-  rc = decode ? launch_decode_ffn(st, 0, up, nZ)
-              : launch_group_gemm(st, 0, up, g.pEC, nZ);
+  rc = aq ? launch_group_gemm_aq(st, 0, up, g.pEC, nZ)
+       : decode ? launch_decode_ffn(st, 0, up, nZ)
+                : launch_group_gemm(st, 0, up, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[3], st));
+  if (aq) {
+    // the intermediate, after activation / gating and its bf16 rounding: a
+    // separate pass over xM (the fused epilogue is an open item, par.5n)
+    rc = launch_quant_g128(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC,
+                           g.P);
+    if (rc != FM_OK) return rc;
+  }
 
   if (g.cfg.dtype == 5 && !mxEpiQuant) {
     // quantize the intermediate activations for the MX down GEMM
@@ -5753,7 +6390,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   GemmArgs dn = up;
   dn.out8 = nullptr;
   dn.outScales = nullptr;
-  dn.A = (g.cfg.dtype == 5) ? (const void*)g.xM8 : g.xM;
+  dn.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.xM8 : g.xM;
   dn.aScales = g.xMs;
   dn.B = reinterpret_cast<const char*>(expert_w) + (size_t)g.P * g.H * g.wesz;
   dn.bias = b_dn;
@@ -5763,8 +6400,9 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   dn.strideAExpert = (long long)g.pEC * g.P;
   dn.K = g.P; dn.N = g.H;
   setWeightScaleArgs(dn, 1, 0, true);
-  rc = decode ? launch_decode_ffn(st, 1, dn, nZ)
-              : launch_group_gemm(st, 1, dn, g.pEC, nZ);
+  rc = aq ? launch_group_gemm_aq(st, 1, dn, g.pEC, nZ)
+       : decode ? launch_decode_ffn(st, 1, dn, nZ)
+                : launch_group_gemm(st, 1, dn, g.pEC, nZ);
   if (rc != FM_OK) return rc;
   if (evs) FM_HIP_CHECK(hipEventRecord(evs[4], st));
 
@@ -5802,7 +6440,8 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                       (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
                       (fusedEnabled() ? 1 : 0))),
                   const_cast<float*>(g.bScale ? g.bScale : g.wScale),
-                  reinterpret_cast<void*>(static_cast<uintptr_t>(g.wScaleGen))};
+                  reinterpret_cast<void*>(static_cast<uintptr_t>(
+                      (uint64_t)g.actQuant << 32 | g.wScaleGen))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
     if (hipGraphLaunch(g.graphExec, st) == hipSuccess) return FM_OK;
     g.graphValid = false;  // replay failed: rebuild next time
@@ -5950,8 +6589,21 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   up.topk = 1; up.act = g.cfg.hidden_act; up.expertOffset = 0;
   up.nRows = (int)n_rows; up.H = g.H;
   setWeightScaleArgs(up, 0, local_e, false);  // like B: pre-offset, stride 0
-  int rc = launch_group_gemm(st, 0, up, (int)n_rows, 1);
+  const bool aq = g.actQuant == 1;  // fp8 activations (par.5n)
+  int rc = FM_OK;
+  if (aq) {
+    rc = launch_quant_g128(st, rows, g.x8, g.xs, n_rows, g.H);
+    if (rc != FM_OK) return rc;
+    up.A = g.x8;
+    up.aScales = g.xs;
+  }
+  rc = aq ? launch_group_gemm_aq(st, 0, up, (int)n_rows, 1)
+          : launch_group_gemm(st, 0, up, (int)n_rows, 1);
   if (rc != FM_OK) return rc;
+  if (aq) {
+    rc = launch_quant_g128(st, g.xM, g.xM8, g.xMs, n_rows, g.P);
+    if (rc != FM_OK) return rc;
+  }
   // note: PHASE 0 with tokenIds==nullptr writes out[e=0 stride 0] = xM rows
   GemmArgs dn = up;
   dn.A = g.xM;
@@ -5961,6 +6613,11 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   dn.out = out_rows;
   dn.K = g.P; dn.N = g.H;
   setWeightScaleArgs(dn, 1, local_e, false);
+  if (aq) {
+    dn.A = g.xM8;
+    dn.aScales = g.xMs;
+    return launch_group_gemm_aq(st, 2, dn, (int)n_rows, 1);
+  }
   return launch_group_gemm(st, 2, dn, (int)n_rows, 1);
 }
 
@@ -6194,8 +6851,14 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
                               (long long)n_segs * g.EC, g.H);
     if (qrc != FM_OK) return qrc;
   }
+  const bool aq = g.actQuant == 1;  // fp8 activations (par.5n)
+  if (aq) {
+    int qrc = launch_quant_g128(st, rows, g.x8, g.xs,
+                                (long long)n_segs * g.EC, g.H);
+    if (qrc != FM_OK) return qrc;
+  }
   GemmArgs up{};
-  up.A = (g.cfg.dtype == 5) ? (const void*)g.x8 : rows;
+  up.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.x8 : rows;
   up.aScales = g.xs;
   up.B = expert_w;
   up.bias = nullptr;
@@ -6224,8 +6887,14 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
     up.out8 = g.xM8;
     up.outScales = g.xMs;
   }
-  int rc = launch_group_gemm(st, 0, up, g.EC, n_segs);
+  int rc = aq ? launch_group_gemm_aq(st, 0, up, g.EC, n_segs)
+              : launch_group_gemm(st, 0, up, g.EC, n_segs);
   if (rc != FM_OK) return rc;
+  if (aq) {
+    int qrc = launch_quant_g128(st, g.xM, g.xM8, g.xMs,
+                                (long long)n_segs * g.EC, g.P);
+    if (qrc != FM_OK) return qrc;
+  }
   if (g.cfg.dtype == 5 && !mxEpiQuant) {
     int qrc = launch_quant_mx(st, g.xM, g.xM8, g.xMs,
                               (long long)n_segs * g.EC, g.P);
@@ -6234,7 +6903,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   GemmArgs dn = up;
   dn.out8 = nullptr;
   dn.outScales = nullptr;
-  dn.A = (g.cfg.dtype == 5) ? (const void*)g.xM8 : g.xM;
+  dn.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.xM8 : g.xM;
   dn.aScales = g.xMs;
   dn.B = reinterpret_cast<const char*>(expert_w) + (size_t)g.P * g.H * g.wesz;
   dn.out = out_rows;
@@ -6243,6 +6912,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   dn.K = g.P;
   dn.N = g.H;
   setWeightScaleArgs(dn, 1, 0, true);
+  if (aq) return launch_group_gemm_aq(st, 2, dn, g.EC, n_segs);
   return launch_group_gemm(st, 2, dn, g.EC, n_segs);
 }
 

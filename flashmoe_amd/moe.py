@@ -266,6 +266,49 @@ def set_weight_block_scales(scales):
     _state["weight_scales"] = scales
 
 
+ACTIVATION_QUANT_MODES = {None: 0, "group128": 1}
+
+
+def set_activation_quant(mode):
+    """fp8 activations for torch_dtype 4. "group128": x
+    and the intermediate are quantised per row in groups of 128 to e4m3 with
+    one fp32 scale each (activation_scheme dynamic of the DeepSeek-V3 / Qwen3
+    FP8 checkpoints) and both expert GEMMs run e4m3 x e4m3 on the fp8 MFMA,
+    with whichever weight scales are attached. None: bf16 activations (the
+    default; initialize and finalize reset to it). Needs H and P multiples of
+    128 and an inference config."""
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    if mode not in ACTIVATION_QUANT_MODES:
+        raise ValueError(f"activation_quant must be None or 'group128'; got "
+                         f"{mode!r}")
+    cfg = _state["cfg"]
+    if mode is not None:
+        if cfg["torch_dtype"] != 4:
+            raise ValueError(
+                f"activation quant needs fp8 expert weights with bf16 "
+                f"activations (torch_dtype 4); the initialized config has "
+                f"torch_dtype {cfg['torch_dtype']}")
+        if cfg["hidden_size"] % 128 or cfg["intermediate_size"] % 128:
+            raise ValueError(
+                f"activation quant needs hidden_size and intermediate_size to "
+                f"be multiples of 128; got {cfg['hidden_size']} and "
+                f"{cfg['intermediate_size']}")
+        if cfg.get("is_training", 0):
+            raise ValueError("activation quant is not supported with "
+                             "is_training 1")
+    _ext.check(_ext.load().fm_set_activation_quant(
+        ACTIVATION_QUANT_MODES[mode]), "fm_set_activation_quant")
+
+
+def get_activation_quant():
+    """The active mode: None or "group128" (fm_get_activation_quant)."""
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    m = _ext.load().fm_get_activation_quant()
+    return {v: k for k, v in ACTIVATION_QUANT_MODES.items()}[m]
+
+
 def get_weight_scales():
     """The attached weight-scale tensor, or None, as the library reports it
     (fm_get_weight_scales). Scales attached through the raw C-ABI are not a
@@ -490,8 +533,11 @@ def _validate_forward_args(input, gate_weights, expert_weights):
     return S, H, E, P, nLx
 
 
+_KEEP = object()  # moe_forward(activation_quant=...): leave the mode as it is
+
+
 def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
-                weight_block_scales=None):
+                weight_block_scales=None, activation_quant=_KEEP):
     """Mirror of _C.moe_forward (python_bindings.cu:17-151): one DMoE
     forward on this rank's tokens. Single-rank path; world>1 uses the EP
     pipeline in ep.py (same result per rank). With
@@ -500,10 +546,17 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
     the shared FFNs. weight_scales (torch_dtype 4 / 5): a
     tensor as for set_weight_scales; one that is not the attached tensor is
     attached first, None leaves the attachment as it is. weight_block_scales
-    (torch_dtype 4): the same for set_weight_block_scales; pass one kind."""
+    (torch_dtype 4): the same for set_weight_block_scales; pass one kind.
+    activation_quant: "group128" or None sets that mode first
+    (set_activation_quant) when it is not the active one; left out, the mode
+    stays as it is."""
     import torch
 
     S, H, E, P, nLx = _validate_forward_args(input, gate_weights, expert_weights)
+    if activation_quant is not _KEEP and (
+            activation_quant not in ACTIVATION_QUANT_MODES or
+            activation_quant != get_activation_quant()):
+        set_activation_quant(activation_quant)
     if weight_scales is not None and weight_scales is not _state["weight_scales"]:
         set_weight_scales(weight_scales)
     if weight_block_scales is not None:

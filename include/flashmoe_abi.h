@@ -232,6 +232,40 @@ int fm_get_weight_scales(const float** scales, int32_t* granularity);
  * 4; hidden_size or intermediate_size not a multiple of 128. */
 int fm_set_weight_block_scales(const float* scales);
 
+/* fp8 activations for the fp8 expert weights (dtype 4 only; DESIGN.md
+ * par.5n): what the W8A8 FP8 checkpoints prescribe (activation_scheme
+ * dynamic, weight_block_size [128, 128]). mode 0: off, bf16 activations (the
+ * default). mode 1, "group128": x [S, H] ahead of the up GEMM and the
+ * intermediate [rows, P] ahead of the down GEMM (after activation / gating
+ * and its bf16 rounding) are quantised per row in groups of 128 along K:
+ *   amax = max|v|, s = amax / 448.0f (1.0f for a zero group),
+ *   q = e4m3_rne(float(v) / s)          (fp32 IEEE divisions, saturating)
+ * and both expert GEMMs run e4m3 x e4m3 on the fp8 MFMA:
+ *   acc[m, n] = sum_kb (sA[m, kb] * sW[n / 128, kb]) * sum_{k in kb} q * w
+ * with sW the attached block scale or 1; a per-channel scale stays in the
+ * epilogue. The gate reads bf16 x. Works with every weight-scale state, gated
+ * experts, shared experts, decode sizes, and is read by fm_moe_forward,
+ * fm_moe_forward_phased, fm_expert_ffn, fm_expert_ffn_segments and
+ * fm_expert_ffn_grouped. Such a forward always runs the multi-kernel path
+ * with the e4m3 x e4m3 grouped GEMMs: FM_FUSED=1 and FM_DECODE_FFN=1 do not
+ * override this, and fm_last_forward_fused / fm_last_forward_decode_ffn
+ * report 0.
+ * Valid after fm_initialize; fm_initialize and fm_finalize reset to 0. A set
+ * call is part of the captured forward graph's key, and the first set to mode
+ * 1 allocates the fp8 and scale workspaces (call it outside a stream capture).
+ * FM_ERR_UNSUPPORTED (the message names the cause; the mode is unchanged): an
+ * unknown mode; mode 1 with a torch_dtype other than 4, with hidden_size or
+ * intermediate_size not a multiple of 128, or with is_training 1.
+ * fm_get_activation_quant returns the mode, or -1 before fm_initialize. */
+int fm_set_activation_quant(int mode);
+int fm_get_activation_quant(void);
+
+/* The group128 quantiser on its own: `in` bf16 [rows, K] (K a multiple of
+ * 128, 16-byte aligned) -> out8 e4m3 bytes [rows, K] and scales fp32
+ * [rows, K / 128], row-major. Needs no fm_initialize. */
+int fm_quant_fp8_g128(void* stream, const void* in, void* out8, float* scales,
+                      int64_t rows, int64_t K);
+
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */
 int fm_get_compiled_config(int64_t* S, int64_t* H, int64_t* E, int64_t* P,

@@ -3,6 +3,7 @@
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
                                    [--router qwen|v2|v3|sigmoid]
                                    [--weight-scales | --weight-block-scales]
+                                   [--activation-quant]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -30,7 +31,10 @@ and reports every run. --weight-scales (dtype 4 and 5 only, DESIGN.md
 par.5l) attaches a random per-output-channel weight-scale tensor,
 exp2(U(-2, 1)) per channel. --weight-block-scales (dtype 4 only, DESIGN.md
 par.5m; H and P multiples of 128) attaches one such scale per 128x128 weight
-block instead.
+block instead. --activation-quant (dtype 4 only; H and P
+multiples of 128) sets set_activation_quant("group128"): fp8 activations and
+the e4m3 x e4m3 expert GEMMs; it composes with both weight-scale flags,
+--hidden-act and --shared.
 """
 import ctypes
 import json
@@ -82,6 +86,9 @@ if weight_scales:
 weight_block_scales = "--weight-block-scales" in argv
 if weight_block_scales:
     argv.remove("--weight-block-scales")
+activation_quant = "--activation-quant" in argv
+if activation_quant:
+    argv.remove("--activation-quant")
 ab_runs = 0
 if "--decode-ab" in argv:
     i = argv.index("--decode-ab")
@@ -104,6 +111,9 @@ if weight_scales and dtype_code not in (4, 5):
 
 if weight_block_scales and (dtype_code != 4 or weight_scales):
     sys.exit("--weight-block-scales needs dtype 4 and excludes --weight-scales")
+
+if activation_quant and dtype_code != 4:
+    sys.exit("--activation-quant needs dtype 4")
 
 adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
@@ -158,6 +168,8 @@ def measure(S):
         moe.set_weight_block_scales(w_scales)
     elif w_scales is not None:
         moe.set_weight_scales(w_scales)
+    if activation_quant:
+        moe.set_activation_quant("group128")
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
     x = x.view(cfg["mini_batch"], cfg["sequence_len"], H)
@@ -241,7 +253,8 @@ def measure(S):
                      + (f" compose={n_compose}" if n_compose else "")
                      + (f" router={router}" if router else "")
                      + (" weight-scales" if weight_scales else "")
-                     + (" weight-block-scales" if weight_block_scales else "")),
+                     + (" weight-block-scales" if weight_block_scales else "")
+                     + (" activation-quant" if activation_quant else "")),
         "us_per_fwd": round(dt * 1e6, 1),
         "tokens_per_s": round(S / dt),
         "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
