@@ -3224,6 +3224,437 @@ void k_group_gemm_aq(GemmArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Per-token fp8 activations for dtype 4 (fm_set_activation_quant(2), "token";
+// DESIGN.md par.5o): k_quant_fp8_g128's rule with the group equal to the row,
+//   amax = max|v| over the row, s = amax / 448 (1.0 for a zero row),
+//   q = e4m3_rne(v / s), both divisions IEEE fp32, saturated at +-448,
+// one fp32 scale per row.
+//
+// Quantiser. A row is split over LPR lanes (8 .. 256, a power of two chosen at
+// launch so that a lane owns at most QR_CH chunks of 16 consecutive elements):
+// chunk c of lane `sub` is chunk c * LPR + sub of the row, so a wave's loads
+// are contiguous. The row is read from HBM once (two 16-byte loads per chunk)
+// and stays in registers as packed bf16 between the amax pass and the
+// conversion pass (one 16-byte store per chunk). Amax: xor-shuffles inside the
+// row's lanes of a wave; a row over 2 or 4 waves (LPR 128 / 256) adds its
+// waves' maxima through LDS, read back in wave order. The trip count is
+// block-uniform. eC != nullptr is the forward's counted entry over the
+// intermediate [nZ, pEC, K]: row r = e * pEC + m is skipped (neither read nor
+// written) when m >= min(eC[e], EC), like the rows the GEMMs do not write;
+// shared-expert slices carry their static counts in eC.
+// ---------------------------------------------------------------------------
+constexpr int QR_CH = 4;  // chunks of 16 elements per lane, at most
+
+template <int LPR>
+__global__ __launch_bounds__(256) FM_NO_PK_F32
+void k_quant_fp8_row(const bf16* __restrict__ in, uint8_t* __restrict__ out8,
+                     float* __restrict__ scales, long long rows, int K,
+                     const uint32_t* __restrict__ eC, int EC, int pEC) {
+  constexpr int RPB = 256 / LPR;              // rows per block
+  constexpr int WPR = LPR > 64 ? LPR / 64 : 1;  // waves per row
+  __shared__ float sMax[2][4];
+  const int sub = threadIdx.x % LPR;
+  const int nCh = K / 16;
+  int it = 0;
+  for (long long base = (long long)blockIdx.x * RPB; base < rows;
+       base += (long long)gridDim.x * RPB, ++it) {
+    const long long r = base + threadIdx.x / LPR;
+    bool live = r < rows;
+    if (live && eC) live = (uint32_t)(r % pEC) < min(eC[r / pEC], (uint32_t)EC);
+    const u32x4* src = reinterpret_cast<const u32x4*>(in + (live ? r : 0) * K);
+    u32x4 w[QR_CH][2];
+    float m = 0.0f;
+#pragma unroll
+    for (int c = 0; c < QR_CH; ++c) {
+      const int ch = c * LPR + sub;
+      const bool on = live && ch < nCh;
+      w[c][0] = on ? src[2 * ch] : u32x4{0u, 0u, 0u, 0u};
+      w[c][1] = on ? src[2 * ch + 1] : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          m = fmaxf(m, fabsf(__uint_as_float(w[c][h][d] << 16)));
+          m = fmaxf(m, fabsf(__uint_as_float(w[c][h][d] & 0xFFFF0000u)));
+        }
+    }
+#pragma unroll
+    for (int off = 1; off < (LPR < 64 ? LPR : 64); off <<= 1)
+      m = fmaxf(m, __shfl_xor(m, off, 64));
+    if constexpr (WPR > 1) {
+      // double-buffered by trip parity: one barrier per trip is enough, the
+      // next write of this slot comes after the next trip's barrier
+      float* sm = sMax[it & 1];
+      if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+      __syncthreads();
+      const int w0 = (threadIdx.x / LPR) * WPR;
+      m = sm[w0];
+#pragma unroll
+      for (int i = 1; i < WPR; ++i) m = fmaxf(m, sm[w0 + i]);
+    }
+    const float s = m > 0.0f ? m / 448.0f : 1.0f;
+    if (!live) continue;  // after the barrier: it is block-uniform
+    u32x4* dst = reinterpret_cast<u32x4*>(out8 + r * K);
+#pragma unroll
+    for (int c = 0; c < QR_CH; ++c) {
+      const int ch = c * LPR + sub;
+      if (ch >= nCh) continue;
+      u32x4 q;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        const uint32_t p0 = w[c][d >> 1][2 * (d & 1)];
+        const uint32_t p1 = w[c][d >> 1][2 * (d & 1) + 1];
+        const float v[4] = {__uint_as_float(p0 << 16),
+                            __uint_as_float(p0 & 0xFFFF0000u),
+                            __uint_as_float(p1 << 16),
+                            __uint_as_float(p1 & 0xFFFF0000u)};
+        float cl[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)  // saturate: v / s may round a hair past 448
+          cl[i] = fminf(fmaxf(v[i] / s, -448.0f), 448.0f);
+        uint32_t pk = __builtin_amdgcn_cvt_pk_fp8_f32(cl[0], cl[1], 0u, false);
+        pk = __builtin_amdgcn_cvt_pk_fp8_f32(cl[2], cl[3], pk, true);
+        q[d] = pk;
+      }
+      dst[ch] = q;
+    }
+    if (sub == 0) scales[r] = s;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Grouped GEMM, per-token e4m3 activations x e4m3 weights (par.5o). The row
+// scale sA[m] and a per-channel weight scale c[n] both factor out of the K
+// sum, so the fp8 MFMA chains its own accumulator across the whole K,
+//   acc[m, n] = sum_k q[m, k] * w[n, k]   (exact products, one fp32 chain),
+// and the epilogue forms (acc * sA[m]) * c[n], in that order, ahead of bias,
+// activation / gating and the combine scale. Against aq_gemm_job_body this
+// drops the zero-C MFMA + fold, both part[] sets, the per-stage sA DMA and
+// its LDS area, and the scalar sW loads.
+//
+// Staging, tiles, swapped operands (lane & 15 = output row), persistent grid
+// with the XCD remap, GATED fragment interleave and PHASE semantics are
+// aq_gemm_job_body's. BN = 128 double-buffers (2 x 32 KiB); BN = 256
+// triple-buffers with counted vmcnt waits of GPW_AB loads per stage in
+// flight. sA: fp32 [rows], one value per tile row, fetched in the prologue
+// with the row's tokenIds entry into LDS beside sTps (up phase: xs[token];
+// down / packed: row e * pEC + m, or m of the packed rows) and read in the
+// epilogue where sScale is read.
+// ---------------------------------------------------------------------------
+template <int BN> __host__ __device__ constexpr int aqt_lds_bytes() {
+  return aq_stages<BN>() * (128 + BN) * 128 + 128 * 8 + 2 * 128 * 4 + 16;
+}
+
+template <int PHASE, bool GATED, int BN>
+__device__ __forceinline__ void aqt_gemm_job_body(const GemmArgs& a,
+                                                  char* smemBase, int e,
+                                                  int m0, int n0) {
+  static_assert(!GATED || (PHASE == 0 && BN == 256),
+                "gated: up phase, 128 P-columns per tile");
+  constexpr int BM = 128, BK = 128;
+  constexpr int SE = aq_stages<BN>();
+  uint8_t* Abase = reinterpret_cast<uint8_t*>(smemBase);   // SE x [BM][BK]
+  uint8_t* Bbase = reinterpret_cast<uint8_t*>(smemBase + SE * BM * BK);
+  TPS* sTps = reinterpret_cast<TPS*>(smemBase + SE * (BM + BN) * BK);
+  float* sScale = reinterpret_cast<float*>(sTps + BM);     // [BM] combine
+  float* sRowA = sScale + BM;                              // [BM] sA
+  uint32_t* sRouted = reinterpret_cast<uint32_t*>(sRowA + BM);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int K = a.K, N = a.N;
+
+  const TPS* tpsE = a.tokenIds ? a.tokenIds + (size_t)e * a.pEC : nullptr;
+  __syncthreads();  // prior job's LDS readers done
+  if (tid == 0)
+    *sRouted = tpsE ? min(a.eC[e], (uint32_t)a.EC) : (uint32_t)a.nRows;
+  __syncthreads();
+  const uint32_t routed = *sRouted;
+  if ((uint32_t)m0 >= routed) return;
+  const int mCap = a.tokenIds ? a.pEC : a.nRows;
+  const int we = a.segExpert ? a.segExpert[e] : e;
+  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
+  const size_t aBase = (size_t)e * a.strideAExpert;  // bytes; a multiple of K
+  if (tid < BM) {
+    TPS t{0u, 1.0f};
+    float sa = 1.0f;
+    if ((uint32_t)(m0 + tid) < routed) {
+      t = tpsE ? tpsE[m0 + tid] : TPS{(uint32_t)(m0 + tid), 1.0f};
+      const size_t arow = (PHASE == 0) ? (size_t)tpsTok(t.tokenIdx)
+                                       : (size_t)(m0 + tid);
+      sa = reinterpret_cast<const float*>(a.aScales)[aBase / (size_t)K + arow];
+    }
+    sTps[tid] = t;
+    sRowA[tid] = sa;
+    if constexpr (PHASE == 1) {
+      float sc = 1.0f;
+      if (scaled && (uint32_t)(m0 + tid) < routed)
+        sc = toF(reinterpret_cast<const bf16*>(
+                 a.gate_out)[(size_t)tpsTok(t.tokenIdx) * a.PX +
+                             a.expertOffset + e]) / t.probSum;
+      sScale[tid] = sc;
+    }
+  }
+  __syncthreads();
+
+  const uint8_t* __restrict__ Ag = reinterpret_cast<const uint8_t*>(a.A);
+  const uint8_t* __restrict__ Bg =
+      reinterpret_cast<const uint8_t*>(a.B) + (size_t)we * a.strideBExpert;
+
+  // staging geometry of mx_gemm_job_body: 1 KiB groups of 8 rows x 128 B
+  const int grow8 = lane >> 3;
+  const int schunk = (lane & 7) ^ grow8;
+  constexpr int GPW_A = BM / 8 / 8;
+  constexpr int GPW_B = BN / 8 / 8;
+  constexpr int GPW_AB = GPW_A + GPW_B;  // loads per wave and stage
+  const uint8_t* aSrc[GPW_A];
+  const uint8_t* bSrc[GPW_B];
+#pragma unroll
+  for (int i = 0; i < GPW_A; ++i) {
+    const int row = (wave * GPW_A + i) * 8 + grow8;
+    const size_t arow = (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
+                                     : (size_t)min(m0 + row, mCap - 1);
+    aSrc[i] = Ag + aBase + arow * (size_t)K + schunk * 16;
+  }
+#pragma unroll
+  for (int i = 0; i < GPW_B; ++i) {
+    const int row = (wave * GPW_B + i) * 8 + grow8;
+    if constexpr (GATED) {
+      const int f = row >> 4;
+      const int prow =
+          min((n0 >> 1) + (f >> 1) * 16 + (row & 15), (N >> 1) - 1);
+      bSrc[i] = Bg + ((f & 1) ? 0 : a.gluOffset) + (size_t)prow * K +
+                schunk * 16;
+    } else {
+      bSrc[i] = Bg + (size_t)min(n0 + row, N - 1) * K + schunk * 16;
+    }
+  }
+  auto stage = [&](int kb, int buf) {
+    const int kt = kb * BK;
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(aSrc[i] + kt),
+          (las_u32*)(Abase + buf * BM * BK + (wave * GPW_A + i) * 1024), 16,
+          0, 0);
+#pragma unroll
+    for (int i = 0; i < GPW_B; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(bSrc[i] + kt),
+          (las_u32*)(Bbase + buf * BN * BK + (wave * GPW_B + i) * 1024), 16,
+          0, 0);
+  };
+
+  const int wr = wave >> 2, wc = wave & 3;
+  constexpr int MI = BM / 32, NF = BN / 64;
+  f32x4 accv[MI][NF];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) accv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int rl = lane & 15;
+  const int gk = lane >> 4;
+  const int nK = K / BK;
+  stage(0, 0);
+  if constexpr (SE == 3) {
+    if (nK > 1) {
+      stage(1, 1);
+      wait_vmcnt<GPW_AB>();  // tile 0 landed; tile 1 in flight
+    } else {
+      wait_vmcnt<0>();
+    }
+  } else {
+    wait_vmcnt<0>();
+  }
+  __builtin_amdgcn_s_barrier();
+  for (int t = 0; t < nK; ++t) {
+    const int pre = t + SE - 1;      // tile staged this iteration
+    const bool stageNow = pre < nK;
+    const uint8_t* Al = Abase + (t % SE) * BM * BK;
+    const uint8_t* Bl = Bbase + (t % SE) * BN * BK;
+    __builtin_amdgcn_s_setprio(1);
+    i32x8 af[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const int R = wr * (BM / 2) + mi * 16 + rl;
+      const int c0 = (2 * gk) ^ (R & 7);
+      const int c1 = (2 * gk + 1) ^ (R & 7);
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(&Al[R * BK + c0 * 16]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(&Al[R * BK + c1 * 16]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        af[mi][d] = (int)lo[d];
+        af[mi][4 + d] = (int)hi[d];
+      }
+    }
+    i32x8 bfr[NF];
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni) {
+      const int R = wc * (BN / 4) + ni * 16 + rl;
+      const int c0 = (2 * gk) ^ (R & 7);
+      const int c1 = (2 * gk + 1) ^ (R & 7);
+      const u32x4 lo = *reinterpret_cast<const u32x4*>(&Bl[R * BK + c0 * 16]);
+      const u32x4 hi = *reinterpret_cast<const u32x4*>(&Bl[R * BK + c1 * 16]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        bfr[ni][d] = (int)lo[d];
+        bfr[ni][4 + d] = (int)hi[d];
+      }
+    }
+    // fragments first, then the next stage, then the MFMAs (par.5n's order:
+    // the compiler's own vmcnt(0) ahead of the LDS reads then only finds the
+    // tile staged one iteration ago)
+    if (stageNow) stage(pre, pre % SE);
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+        accv[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            bfr[ni], af[mi], accv[mi][ni], 0 /*fp8*/, 0 /*fp8*/, 0, 0x7F, 0,
+            0x7F);
+    __builtin_amdgcn_s_setprio(0);
+    if constexpr (SE == 3) {
+      if (stageNow) wait_vmcnt<GPW_AB>(); else wait_vmcnt<0>();
+    } else {
+      wait_vmcnt<0>();
+    }
+    __builtin_amdgcn_s_barrier();
+  }
+
+  // epilogue: lane & 15 is the row of fragment mi, accv[mi][ni][0..3] are
+  // columns cq..cq+3 of fragment ni. Reads sTps / sScale / sRowA only.
+  // The lane's coordinates are taken again from an opaque copy of tid, so
+  // that the epilogue's loop invariants (columns, rows, pointers) are formed
+  // here and not hoisted above the K loop, where they cost the BN = 128
+  // kernels the registers that two blocks per CU leave (128).
+  int tidE = tid;
+  asm volatile("" : "+v"(tidE));
+  const int rlE = tidE & 15;
+  const int waveE = __builtin_amdgcn_readfirstlane(tidE >> 6);
+  const int wrE = waveE >> 2, wcE = waveE & 3;
+  const int cq = ((tidE & 63) >> 4) * 4;
+  const int act = a.act;
+  const int nOut = GATED ? (N >> 1) : N;  // output columns (and row pitch)
+  constexpr int NOUT = GATED ? NF / 2 : NF;
+  const int oBase =
+      (GATED ? (n0 >> 1) + wcE * (BN / 8) : n0 + wcE * (BN / 4)) + cq;
+  float bv[NOUT][4], sv[NF][4];
+#pragma unroll
+  for (int no = 0; no < NOUT; ++no)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bv[no][r] = 0.f;
+  if (a.bias) {
+    const bf16* bptr = reinterpret_cast<const bf16*>(a.bias) +
+                       (a.strideBExpert ? (size_t)we * nOut : 0);
+#pragma unroll
+    for (int no = 0; no < NOUT; ++no)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int col = oBase + no * 16 + r;
+        if (col < nOut) bv[no][r] = toF(bptr[col]);
+      }
+  }
+  {
+    const float* sp =
+        a.wScale ? a.wScale + (size_t)we * a.wScaleStride : nullptr;
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (GATED)
+          sv[ni][r] = wscale_at(
+              sp ? sp + ((ni & 1) ? 0 : a.wScaleGlu) : nullptr,
+              oBase + (ni >> 1) * 16 + r, nOut);
+        else
+          sv[ni][r] = wscale_at(sp, oBase + ni * 16 + r, nOut);
+      }
+  }
+  bf16* outBase;
+  if constexpr (PHASE == 1)
+    outBase = reinterpret_cast<bf16*>(slot ? (void*)a.O32 : a.moe_out);
+  else
+    outBase = reinterpret_cast<bf16*>(a.out) + (size_t)e * a.strideOExpert;
+  const long long rowPitch = (PHASE == 1) ? a.H : nOut;
+  const bool vecOK = (rowPitch & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(outBase) & 7) == 0;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int row = wrE * (BM / 2) + mi * 16 + rlE;
+    const int m = m0 + row;
+    if ((uint32_t)m >= routed) continue;  // rows past routed: not written
+    bf16* orow;
+    float rowScale = 1.0f;
+    const float sa = sRowA[row];
+    if constexpr (PHASE == 1) {
+      const TPS tp = sTps[row];
+      if (slot) {
+        orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
+                          tpsJ(tp.tokenIdx)) * rowPitch;
+        rowScale = sScale[row];
+      } else {
+        orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+      }
+    } else {
+      orow = outBase + (size_t)m * rowPitch;
+    }
+#pragma unroll
+    for (int no = 0; no < NOUT; ++no) {
+      const int col0 = oBase + no * 16;
+      const int nValid = nOut - col0;
+      if (nValid <= 0) continue;  // columns >= N are not written
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (GATED) {
+          v[r] = gate_act((accv[mi][2 * no][r] * sa) * sv[2 * no][r], act) *
+                 ((accv[mi][2 * no + 1][r] * sa) * sv[2 * no + 1][r]);
+        } else {
+          v[r] = (accv[mi][no][r] * sa) * sv[no][r] + bv[no][r];
+          if constexpr (PHASE == 0)
+            v[r] = (act == 0)
+                ? fmaxf(v[r], 0.0f)
+                : 0.5f * v[r] * (1.0f + erff(v[r] * 0.70710678118654752f));
+          if constexpr (PHASE == 1)
+            if (slot) v[r] = v[r] * rowScale;
+        }
+      }
+      storeRow4<false>(orow + col0, v, nValid, vecOK);
+    }
+  }
+}
+
+// BN = 128: 66 KiB of LDS and at most 128 VGPRs, two blocks per CU (what its
+// persistent grid assumes); BN = 256: 146 KiB, one block per CU.
+template <int PHASE, bool GATED, int BN>
+__global__ __launch_bounds__(512, BN == 256 ? 1 : 4) FM_NO_PK_F32
+void k_group_gemm_aqt(GemmArgs a) {
+  constexpr int BM = 128;
+  __shared__ __attribute__((aligned(16))) char smem[aqt_lds_bytes<BN>()];
+  const int mT = a.totalJobs > 0 ? a.jobsMT : gridDim.x;
+  const int nT = a.totalJobs > 0 ? a.jobsNT : gridDim.y;
+  const int gstride = gridDim.x * gridDim.y * gridDim.z;
+  const int nBlocks = a.totalJobs > 0 ? a.totalJobs : gstride;
+  const int lin0 =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int qx = nBlocks / 8, rx = nBlocks % 8;
+  for (int jl = lin0; jl < nBlocks; jl += gstride) {
+    const int xcd = jl % 8, pos = jl / 8;
+    const int swz = a.noRemap
+        ? jl
+        : (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+    const int e = swz / (mT * nT);
+    const int rem = swz % (mT * nT);
+    aqt_gemm_job_body<PHASE, GATED, BN>(a, smem, e, (rem % mT) * BM,
+                                        (rem / mT) * BN);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fp32 grouped GEMM (config-1 "CPU correctness plumbing" shapes; VALU
 // tiled). 64x64 tile, 256 threads, each thread a 4x4 sub-block, BK=16.
 // Same phase semantics as the bf16 kernel.
@@ -4554,6 +4985,10 @@ static int launch_group_gemm(hipStream_t st, int phase, const struct GemmArgs& a
 static int launch_quant_g128(hipStream_t st, const void* in, uint8_t* out,
                              uint8_t* scales, long long nRows, int K,
                              int sPitch = 0);
+static int launch_quant_row(hipStream_t st, const void* in, uint8_t* out,
+                            uint8_t* scales, long long nRows, int K,
+                            const uint32_t* eC = nullptr, int EC = 0,
+                            int pEC = 1);
 
 namespace {
 
@@ -4610,7 +5045,8 @@ struct State {
   uint8_t* xMs = nullptr;    // dtype 5: xM block scales
   // (dtype 4 with fm_set_activation_quant(1), DESIGN.md par.5n: the same four,
   // allocated by the set call; xs / xMs then hold fp32 [rows, K/128])
-  int actQuant = 0;          // 0 off, 1 group128; part of the graph key
+  int actQuant = 0;          // 0 off, 1 group128, 2 token (par.5o: xs / xMs
+                             // hold fp32 [rows]); part of the graph key
   float* O32 = nullptr;      // [S, H] (staged-API combine accumulator)
   void* cbuf = nullptr;      // [S, k, H] Element: non-atomic combine slots
   uint8_t* kept = nullptr;   // [S, k] capacity-kept mask (gate-written)
@@ -5617,6 +6053,12 @@ int fm_set_weight_block_scales(const float* scales) {
              "intermediate_size %d", g.H, g.P);
     return FM_ERR_UNSUPPORTED;
   }
+  if (scales && g.actQuant == 2) {
+    setErr("weight block scales are not supported while activation quant "
+           "token is active: a per-token scale pairs with per-channel weight "
+           "scales (block scales pair with activation quant group128)");
+    return FM_ERR_UNSUPPORTED;
+  }
   g.bScale = scales;
   g.wScale = nullptr;  // one kind of scale at a time
   g.wScaleGran = scales ? 2 : 0;
@@ -5626,35 +6068,53 @@ int fm_set_weight_block_scales(const float* scales) {
 
 int fm_set_activation_quant(int mode) {
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
-  if (mode != 0 && mode != 1) {
+  if (mode != 0 && mode != 1 && mode != 2) {
     snprintf(g_err, sizeof(g_err),
-             "activation quant mode must be 0 (off) or 1 (group128); got %d",
-             mode);
+             "activation quant mode must be 0 (off), 1 (group128) or 2 "
+             "(token); got %d", mode);
     return FM_ERR_UNSUPPORTED;
   }
-  if (mode == 1) {
+  if (mode != 0) {
+    const char* name = mode == 1 ? "group128" : "token";
     if (g.cfg.dtype != 4) {
       snprintf(g_err, sizeof(g_err),
-               "activation quant group128 needs fp8 expert weights with bf16 "
+               "activation quant %s needs fp8 expert weights with bf16 "
                "activations: torch_dtype must be 4, the config has torch_dtype "
-               "%d", (int)g.cfg.dtype);
+               "%d", name, (int)g.cfg.dtype);
       return FM_ERR_UNSUPPORTED;
     }
     if (g.H % 128 != 0 || g.P % 128 != 0) {
       snprintf(g_err, sizeof(g_err),
-               "activation quant group128 needs hidden_size and "
+               "activation quant %s needs hidden_size and "
                "intermediate_size to be multiples of the 128 group; got "
-               "hidden_size %d, intermediate_size %d", g.H, g.P);
+               "hidden_size %d, intermediate_size %d", name, g.H, g.P);
       return FM_ERR_UNSUPPORTED;
     }
     if (g.cfg.is_training) {
-      setErr("activation quant group128 is not supported with is_training 1 "
-             "(inference only)");
+      snprintf(g_err, sizeof(g_err),
+               "activation quant %s is not supported with is_training 1 "
+               "(inference only)", name);
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (mode == 2 && g.bScale) {
+      setErr("activation quant token is not supported while weight block "
+             "scales are attached: a per-token scale pairs with per-channel "
+             "weight scales (block scales pair with activation quant "
+             "group128)");
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (mode == 2 && std::max(g.H, g.P) > 16 * 256 * QR_CH) {
+      snprintf(g_err, sizeof(g_err),
+               "activation quant token holds a row in one block's registers: "
+               "hidden_size and intermediate_size up to %d; got %d and %d",
+               16 * 256 * QR_CH, g.H, g.P);
       return FM_ERR_UNSUPPORTED;
     }
     if (!g.x8) {
       // here, outside any capture; sized like the dtype-5 workspaces for
-      // the forward (S rows) and the EP entry points (nLxAlloc * pEC rows)
+      // the forward (S rows) and the EP entry points (nLxAlloc * pEC rows).
+      // The scale workspaces serve either mode: token needs one float per
+      // row, group128's pitch is at least four
       const size_t qRows = std::max((size_t)g.S, (size_t)g.nLxAlloc * g.pEC);
       uint8_t *a8 = nullptr, *as = nullptr, *m8 = nullptr, *ms = nullptr;
       const bool ok =
@@ -5693,6 +6153,30 @@ int fm_quant_fp8_g128(void* stream, const void* in, void* out8, float* scales,
                            reinterpret_cast<uint8_t*>(out8),
                            reinterpret_cast<uint8_t*>(scales), rows, (int)K,
                            (int)(K / 128));
+}
+
+int fm_quant_fp8_row(void* stream, const void* in, void* out8, float* scales,
+                     int64_t rows, int64_t K) {
+  return fm_quant_fp8_row_counted(stream, in, out8, scales, nullptr, 1, rows,
+                                  rows, K);
+}
+
+int fm_quant_fp8_row_counted(void* stream, const void* in, void* out8,
+                             float* scales, const uint32_t* counts,
+                             int64_t n_slices, int64_t pitch_rows, int64_t cap,
+                             int64_t K) {
+  if (n_slices < 0 || pitch_rows < 0 || K <= 0 || K % 128 != 0 ||
+      K > 16 * 256 * QR_CH) {
+    snprintf(g_err, sizeof(g_err),
+             "fm_quant_fp8_row: K must be a positive multiple of 128, at most "
+             "%d", 16 * 256 * QR_CH);
+    return FM_ERR_SHAPE;
+  }
+  return launch_quant_row(reinterpret_cast<hipStream_t>(stream), in,
+                          reinterpret_cast<uint8_t*>(out8),
+                          reinterpret_cast<uint8_t*>(scales),
+                          n_slices * pitch_rows, (int)K, counts, (int)cap,
+                          (int)std::max<int64_t>(pitch_rows, 1));
 }
 
 int fm_get_weight_scales(const float** scales, int32_t* granularity) {
@@ -6217,11 +6701,48 @@ static int launch_quant_g128(hipStream_t st, const void* in, uint8_t* out,
   return FM_OK;
 }
 
+// fm_set_activation_quant(2): bf16 rows -> e4m3 + one fp32 scale per row
+// (par.5o). The row is split over the fewest lanes that keep a lane within
+// QR_CH chunks of 16 elements: 8 lanes up to K 512, 16 up to 1024 (K 768: 16
+// rows per block, every lane busy) ... 256 lanes, four waves, from K 8320 to
+// 16384. eC: the counted entry over [nRows / pEC, pEC] (k_quant_fp8_row).
+static int launch_quant_row(hipStream_t st, const void* in, uint8_t* out,
+                            uint8_t* scales, long long nRows, int K,
+                            const uint32_t* eC, int EC, int pEC) {
+  if (nRows <= 0) return FM_OK;
+  int lpr = 8;
+  while (DIVUP(K / 16, lpr) > QR_CH && lpr < 256) lpr *= 2;
+  const int grid = (int)std::min<long long>(DIVUP(nRows, 256 / lpr), 8192);
+#define QROW(L)                                                               \
+  case L:                                                                     \
+    hipLaunchKernelGGL(k_quant_fp8_row<L>, dim3(grid), dim3(256), 0, st,      \
+                       reinterpret_cast<const bf16*>(in), out,                \
+                       reinterpret_cast<float*>(scales), nRows, K, eC, EC,    \
+                       pEC);                                                  \
+    break
+  switch (lpr) {
+    QROW(8); QROW(16); QROW(32); QROW(64); QROW(128); QROW(256);
+  }
+#undef QROW
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
+// the quantiser of the active mode over plain rows (x, packed EP rows)
+static int launch_quant_act(hipStream_t st, const void* in, uint8_t* out,
+                            uint8_t* scales, long long nRows, int K) {
+  return g.actQuant == 2 ? launch_quant_row(st, in, out, scales, nRows, K)
+                         : launch_quant_g128(st, in, out, scales, nRows, K);
+}
+
 // fm_set_activation_quant(1): the e4m3 x e4m3 grouped GEMM (par.5n). The
 // caller describes the plain problem like launch_group_gemm's callers, with
 // a.A / a.aScales the quantised rows. Up phase: 128 output columns per tile
 // (ungated BN = 128; gated the effective BN = 256). Down / packed phase:
 // 128x256 where N affords it and the grid fills the chip, else 128x128.
+// fm_set_activation_quant(2) (par.5o) launches k_group_gemm_aqt on the same
+// grids; without a quantisation group to respect, its ungated up phase takes
+// the 128x256 tile under the down phase's rule.
 static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
                                 int M, int nE) {
   const bool gated = phase == 0 && a.act >= 2;
@@ -6236,8 +6757,9 @@ static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
   aa.noRemap = 0;
   aa.totalJobs = 0;
   const int nCU = g.nCU > 0 ? g.nCU : 256;
+  const bool tok = g.actQuant == 2;
   const bool wide =
-      gated || (phase != 0 && aa.N >= 256 &&
+      gated || ((phase != 0 || tok) && aa.N >= 256 &&
                 DIVUP(M, 128) * DIVUP(aa.N, 256) * nE >= nCU);
   dim3 grid(DIVUP(M, 128), DIVUP(aa.N, wide ? 256 : 128), nE);
   const int J = grid.x * grid.y * nE;
@@ -6248,6 +6770,26 @@ static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
     aa.jobsNT = grid.y;
     grid = dim3(resident, 1, 1);
   }
+#define AQTGG(PH)                                                             \
+  do {                                                                        \
+    if (wide)                                                                 \
+      hipLaunchKernelGGL((k_group_gemm_aqt<PH, false, 256>), grid, dim3(512), \
+                         0, st, aa);                                          \
+    else                                                                      \
+      hipLaunchKernelGGL((k_group_gemm_aqt<PH, false, 128>), grid, dim3(512), \
+                         0, st, aa);                                          \
+  } while (0)
+  if (tok) {
+    if (gated)
+      hipLaunchKernelGGL((k_group_gemm_aqt<0, true, 256>), grid, dim3(512), 0,
+                         st, aa);
+    else if (phase == 0) AQTGG(0);
+    else if (phase == 1) AQTGG(1);
+    else AQTGG(2);
+    FM_HIP_CHECK(hipGetLastError());
+    return FM_OK;
+  }
+#undef AQTGG
 #define AQGG(PH)                                                              \
   do {                                                                        \
     if (wide)                                                                 \
@@ -6290,9 +6832,9 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // (nor does a decode-sized forward, S < 128: no ragged tile there)
   // (nor does a forward with weight scales attached: k_moe_fused is not
   // taught about them, its GemmArgs carry none)
-  // (nor does a forward with fp8 activations, fm_set_activation_quant(1):
+  // (nor does a forward with fp8 activations, fm_set_activation_quant(1 / 2):
   // it runs the e4m3 x e4m3 GEMMs, whatever FM_FUSED says)
-  const bool aq = g.actQuant == 1;
+  const bool aq = g.actQuant != 0;
   if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
       g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV &&
       !g.wScale && !g.bScale && !aq) {
@@ -6325,8 +6867,8 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
     rc = launch_quant_mx(st, x, g.x8, g.xs, g.S, g.H);
     if (rc != FM_OK) return rc;
   }
-  if (aq) {  // group128: x once, after the gate (which read bf16 x)
-    rc = launch_quant_g128(st, x, g.x8, g.xs, g.S, g.H);
+  if (aq) {  // x once, after the gate (which read bf16 x)
+    rc = launch_quant_act(st, x, g.x8, g.xs, g.S, g.H);
     if (rc != FM_OK) return rc;
   }
 
@@ -6375,8 +6917,12 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   if (aq) {
     // the intermediate, after activation / gating and its bf16 rounding: a
     // separate pass over xM (the fused epilogue is an open item, par.5n)
-    rc = launch_quant_g128(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC,
-                           g.P);
+    // (token: only the rows the up GEMM wrote, m < min(eC[e], EC))
+    rc = g.actQuant == 2
+        ? launch_quant_row(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC, g.P,
+                           g.eC, g.EC, g.pEC)
+        : launch_quant_g128(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC,
+                            g.P);
     if (rc != FM_OK) return rc;
   }
 
@@ -6589,10 +7135,10 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   up.topk = 1; up.act = g.cfg.hidden_act; up.expertOffset = 0;
   up.nRows = (int)n_rows; up.H = g.H;
   setWeightScaleArgs(up, 0, local_e, false);  // like B: pre-offset, stride 0
-  const bool aq = g.actQuant == 1;  // fp8 activations (par.5n)
+  const bool aq = g.actQuant != 0;  // fp8 activations (par.5n, 5o)
   int rc = FM_OK;
   if (aq) {
-    rc = launch_quant_g128(st, rows, g.x8, g.xs, n_rows, g.H);
+    rc = launch_quant_act(st, rows, g.x8, g.xs, n_rows, g.H);
     if (rc != FM_OK) return rc;
     up.A = g.x8;
     up.aScales = g.xs;
@@ -6601,7 +7147,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
           : launch_group_gemm(st, 0, up, (int)n_rows, 1);
   if (rc != FM_OK) return rc;
   if (aq) {
-    rc = launch_quant_g128(st, g.xM, g.xM8, g.xMs, n_rows, g.P);
+    rc = launch_quant_act(st, g.xM, g.xM8, g.xMs, n_rows, g.P);
     if (rc != FM_OK) return rc;
   }
   // note: PHASE 0 with tokenIds==nullptr writes out[e=0 stride 0] = xM rows
@@ -6851,10 +7397,10 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
                               (long long)n_segs * g.EC, g.H);
     if (qrc != FM_OK) return qrc;
   }
-  const bool aq = g.actQuant == 1;  // fp8 activations (par.5n)
+  const bool aq = g.actQuant != 0;  // fp8 activations (par.5n, 5o)
   if (aq) {
-    int qrc = launch_quant_g128(st, rows, g.x8, g.xs,
-                                (long long)n_segs * g.EC, g.H);
+    int qrc = launch_quant_act(st, rows, g.x8, g.xs,
+                               (long long)n_segs * g.EC, g.H);
     if (qrc != FM_OK) return qrc;
   }
   GemmArgs up{};
@@ -6891,8 +7437,8 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
               : launch_group_gemm(st, 0, up, g.EC, n_segs);
   if (rc != FM_OK) return rc;
   if (aq) {
-    int qrc = launch_quant_g128(st, g.xM, g.xM8, g.xMs,
-                                (long long)n_segs * g.EC, g.P);
+    int qrc = launch_quant_act(st, g.xM, g.xM8, g.xMs,
+                               (long long)n_segs * g.EC, g.P);
     if (qrc != FM_OK) return qrc;
   }
   if (g.cfg.dtype == 5 && !mxEpiQuant) {

@@ -251,6 +251,9 @@ def set_weight_block_scales(scales):
             f"weight block scales need hidden_size and intermediate_size to be "
             f"multiples of 128; got {cfg['hidden_size']} and "
             f"{cfg['intermediate_size']}")
+    if lib.fm_get_activation_quant() == ACTIVATION_QUANT_MODES["token"]:
+        raise ValueError("weight block scales are not supported while "
+                         "activation quant token is active")
     want = _weight_block_scale_shape()
     if not isinstance(scales, torch.Tensor) or not scales.is_cuda or \
             scales.dtype != torch.float32 or tuple(scales.shape) != want or \
@@ -266,7 +269,7 @@ def set_weight_block_scales(scales):
     _state["weight_scales"] = scales
 
 
-ACTIVATION_QUANT_MODES = {None: 0, "group128": 1}
+ACTIVATION_QUANT_MODES = {None: 0, "group128": 1, "token": 2}
 
 
 def set_activation_quant(mode):
@@ -274,14 +277,17 @@ def set_activation_quant(mode):
     and the intermediate are quantised per row in groups of 128 to e4m3 with
     one fp32 scale each (activation_scheme dynamic of the DeepSeek-V3 / Qwen3
     FP8 checkpoints) and both expert GEMMs run e4m3 x e4m3 on the fp8 MFMA,
-    with whichever weight scales are attached. None: bf16 activations (the
+    with whichever weight scales are attached. "token" (par.5o): one scale
+    for the whole row (compressed-tensors FP8-dynamic: activations strategy
+    token, dynamic true), with per-channel weight scales or none; it and
+    weight block scales exclude each other. None: bf16 activations (the
     default; initialize and finalize reset to it). Needs H and P multiples of
     128 and an inference config."""
     if not _state["initialized"]:
         raise RuntimeError("Must call initialize() first")
     if mode not in ACTIVATION_QUANT_MODES:
-        raise ValueError(f"activation_quant must be None or 'group128'; got "
-                         f"{mode!r}")
+        raise ValueError(f"activation_quant must be None, 'group128' or "
+                         f"'token'; got {mode!r}")
     cfg = _state["cfg"]
     if mode is not None:
         if cfg["torch_dtype"] != 4:
@@ -297,12 +303,18 @@ def set_activation_quant(mode):
         if cfg.get("is_training", 0):
             raise ValueError("activation quant is not supported with "
                              "is_training 1")
+        gran = ctypes.c_int32(0)
+        _ext.load().fm_get_weight_scales(None, ctypes.byref(gran))
+        if mode == "token" and gran.value == 2:
+            raise ValueError("activation quant token is not supported while "
+                             "weight block scales are attached")
     _ext.check(_ext.load().fm_set_activation_quant(
         ACTIVATION_QUANT_MODES[mode]), "fm_set_activation_quant")
 
 
 def get_activation_quant():
-    """The active mode: None or "group128" (fm_get_activation_quant)."""
+    """The active mode: None, "group128" or "token"
+    (fm_get_activation_quant)."""
     if not _state["initialized"]:
         raise RuntimeError("Must call initialize() first")
     m = _ext.load().fm_get_activation_quant()
@@ -547,7 +559,7 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
     tensor as for set_weight_scales; one that is not the attached tensor is
     attached first, None leaves the attachment as it is. weight_block_scales
     (torch_dtype 4): the same for set_weight_block_scales; pass one kind.
-    activation_quant: "group128" or None sets that mode first
+    activation_quant: "group128", "token" or None sets that mode first
     (set_activation_quant) when it is not the active one; left out, the mode
     stays as it is."""
     import torch

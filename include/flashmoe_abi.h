@@ -229,7 +229,8 @@ int fm_get_weight_scales(const float** scales, int32_t* granularity);
  * the small synchronous kernel have no block-scale variant; FM_FORCE_MODE 0
  * and 2 are mapped like the default choice).
  * FM_ERR_UNSUPPORTED (the message names the cause): a torch_dtype other than
- * 4; hidden_size or intermediate_size not a multiple of 128. */
+ * 4; hidden_size or intermediate_size not a multiple of 128; a non-null
+ * tensor while activation quant mode 2 (token) is active (nothing changes). */
 int fm_set_weight_block_scales(const float* scales);
 
 /* fp8 activations for the fp8 expert weights (dtype 4 only; DESIGN.md
@@ -250,12 +251,28 @@ int fm_set_weight_block_scales(const float* scales);
  * with the e4m3 x e4m3 grouped GEMMs: FM_FUSED=1 and FM_DECODE_FFN=1 do not
  * override this, and fm_last_forward_fused / fm_last_forward_decode_ffn
  * report 0.
+ * mode 2, "token" (DESIGN.md par.5o): what the compressed-tensors FP8-dynamic
+ * checkpoints prescribe (activations strategy token, dynamic true, over
+ * per-channel weight scales). The same two tensors are quantised by the same
+ * rule with the group equal to the whole row, one fp32 scale sA[m] per row:
+ *   amax = max|v| over the row, s = amax / 448.0f (1.0f for a zero row),
+ *   q = e4m3_rne(float(v) / s)          (fp32 IEEE divisions, saturating)
+ * Both scales factor out of the K sum, so one fp32 MFMA accumulator runs over
+ * the whole K and the epilogue applies them once, in this order:
+ *   acc[m, n] = sum_k q[m, k] * w[n, k];   v = (acc * sA[m]) * c[n]
+ * with c the attached per-channel scale or 1; bias, activation / gating, the
+ * combine scale and shared slices follow as in mode 1. No atomics: two
+ * forwards are bit-identical. Everything else said of mode 1 holds, except
+ * that mode 2 and weight block scales exclude each other.
  * Valid after fm_initialize; fm_initialize and fm_finalize reset to 0. A set
- * call is part of the captured forward graph's key, and the first set to mode
- * 1 allocates the fp8 and scale workspaces (call it outside a stream capture).
+ * call is part of the captured forward graph's key, and the first set to a
+ * non-zero mode allocates the fp8 and scale workspaces, which serve both modes
+ * (call it outside a stream capture).
  * FM_ERR_UNSUPPORTED (the message names the cause; the mode is unchanged): an
- * unknown mode; mode 1 with a torch_dtype other than 4, with hidden_size or
- * intermediate_size not a multiple of 128, or with is_training 1.
+ * unknown mode; mode 1 or 2 with a torch_dtype other than 4, with hidden_size
+ * or intermediate_size not a multiple of 128, or with is_training 1; mode 2
+ * while weight block scales are attached, or with hidden_size or
+ * intermediate_size above 16384.
  * fm_get_activation_quant returns the mode, or -1 before fm_initialize. */
 int fm_set_activation_quant(int mode);
 int fm_get_activation_quant(void);
@@ -265,6 +282,19 @@ int fm_get_activation_quant(void);
  * [rows, K / 128], row-major. Needs no fm_initialize. */
 int fm_quant_fp8_g128(void* stream, const void* in, void* out8, float* scales,
                       int64_t rows, int64_t K);
+
+/* The token quantiser on its own: `in` bf16 [rows, K] (K a multiple of 128,
+ * at most 16384, 16-byte aligned) -> out8 e4m3 bytes [rows, K] and scales
+ * fp32 [rows]. Needs no fm_initialize. The counted form walks
+ * [n_slices, pitch_rows] rows and leaves row m of slice e untouched (not
+ * read, not written) when m >= min(counts[e], cap); counts is a device
+ * pointer. It is the forward's pass over the intermediate. */
+int fm_quant_fp8_row(void* stream, const void* in, void* out8, float* scales,
+                     int64_t rows, int64_t K);
+int fm_quant_fp8_row_counted(void* stream, const void* in, void* out8,
+                             float* scales, const uint32_t* counts,
+                             int64_t n_slices, int64_t pitch_rows, int64_t cap,
+                             int64_t K);
 
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */

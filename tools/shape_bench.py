@@ -3,7 +3,7 @@
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
                                    [--router qwen|v2|v3|sigmoid]
                                    [--weight-scales | --weight-block-scales]
-                                   [--activation-quant]
+                                   [--activation-quant [group128|token]]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -32,7 +32,9 @@ par.5l) attaches a random per-output-channel weight-scale tensor,
 exp2(U(-2, 1)) per channel. --weight-block-scales (dtype 4 only, DESIGN.md
 par.5m; H and P multiples of 128) attaches one such scale per 128x128 weight
 block instead. --activation-quant (dtype 4 only; H and P
-multiples of 128) sets set_activation_quant("group128"): fp8 activations and
+multiples of 128) sets set_activation_quant("group128"), or with the word
+token set_activation_quant("token") (par.5o; not with --weight-block-scales):
+fp8 activations and
 the e4m3 x e4m3 expert GEMMs; it composes with both weight-scale flags,
 --hidden-act and --shared.
 """
@@ -86,9 +88,13 @@ if weight_scales:
 weight_block_scales = "--weight-block-scales" in argv
 if weight_block_scales:
     argv.remove("--weight-block-scales")
-activation_quant = "--activation-quant" in argv
-if activation_quant:
-    argv.remove("--activation-quant")
+activation_quant = None
+if "--activation-quant" in argv:
+    i = argv.index("--activation-quant")
+    argv.pop(i)
+    activation_quant = "group128"  # the bare flag
+    if i < len(argv) and argv[i] in ("group128", "token"):
+        activation_quant = argv.pop(i)
 ab_runs = 0
 if "--decode-ab" in argv:
     i = argv.index("--decode-ab")
@@ -169,7 +175,7 @@ def measure(S):
     elif w_scales is not None:
         moe.set_weight_scales(w_scales)
     if activation_quant:
-        moe.set_activation_quant("group128")
+        moe.set_activation_quant(activation_quant)
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
     x = x.view(cfg["mini_batch"], cfg["sequence_len"], H)
@@ -254,7 +260,8 @@ def measure(S):
                      + (f" router={router}" if router else "")
                      + (" weight-scales" if weight_scales else "")
                      + (" weight-block-scales" if weight_block_scales else "")
-                     + (" activation-quant" if activation_quant else "")),
+                     + (" activation-quant" if activation_quant else "")
+                     + ("=token" if activation_quant == "token" else "")),
         "us_per_fwd": round(dt * 1e6, 1),
         "tokens_per_s": round(S / dt),
         "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
