@@ -11,11 +11,13 @@ from flashmoe_amd import (  # noqa: F401
     initialize,
     moe_forward,
     pack_weight_block_scales,
+    pack_weight_mx_scales,
     pack_weight_scales,
     run_moe,
     set_activation_quant,
     set_score_bias,
     set_weight_block_scales,
+    set_weight_mx_scales,
     set_weight_scales,
 )
 from flashmoe_amd import moe as _C  # noqa: F401  (the _C-equivalent surface)

@@ -15,10 +15,12 @@ from .moe import (  # noqa: F401
     initialize,
     moe_forward,
     pack_weight_block_scales,
+    pack_weight_mx_scales,
     pack_weight_scales,
     set_activation_quant,
     set_score_bias,
     set_weight_block_scales,
+    set_weight_mx_scales,
     set_weight_scales,
 )
 from .ops import run_moe  # noqa: F401
@@ -39,6 +41,8 @@ __all__ = [
     "pack_weight_scales",
     "set_weight_block_scales",
     "pack_weight_block_scales",
+    "set_weight_mx_scales",
+    "pack_weight_mx_scales",
     "set_activation_quant",
     "get_activation_quant",
 ]

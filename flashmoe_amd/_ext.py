@@ -65,6 +65,8 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_set_weight_scales.restype = ctypes.c_int
     lib.fm_set_weight_block_scales.argtypes = [p]
     lib.fm_set_weight_block_scales.restype = ctypes.c_int
+    lib.fm_set_weight_mx_scales.argtypes = [p]
+    lib.fm_set_weight_mx_scales.restype = ctypes.c_int
     lib.fm_set_activation_quant.argtypes = [ctypes.c_int]
     lib.fm_set_activation_quant.restype = ctypes.c_int
     lib.fm_get_activation_quant.argtypes = []

@@ -23,14 +23,17 @@ REQUIRED_KEYS = [
 # config-5 "fp8 weights / bf16 accumulate" regime), 5 MX fp8: fp8e4m3
 # weights AND runtime-quantized fp8 activations (per-64-element E8M0
 # block scales) on the CDNA4 scaled MFMA - the 2x-rate path (extension
-# codes; the reference schema stops at 3). torch_dtype_of() is the
+# codes; the reference schema stops at 3), 6 MXFP4 expert weights (OCP e2m1,
+# two per byte, one E8M0 scale per 32 along K) with bf16 activations - W4A16,
+# what gpt-oss ships. torch_dtype_of() is the
 # ACTIVATION dtype at the API boundary; weight_dtype_of() the
 # expert-weight storage dtype.
 def torch_dtype_of(code: int):
     import torch
 
     return {0: torch.float32, 1: torch.float32, 2: torch.bfloat16,
-            3: torch.float16, 4: torch.bfloat16, 5: torch.bfloat16}[code]
+            3: torch.float16, 4: torch.bfloat16, 5: torch.bfloat16,
+            6: torch.bfloat16}[code]
 
 
 def weight_dtype_of(code: int):
@@ -38,12 +41,14 @@ def weight_dtype_of(code: int):
 
     if code in (4, 5):
         return torch.float8_e4m3fn
+    if code == 6:
+        return torch.uint8  # packed e2m1 pairs: [.., P, H/2]
     return torch_dtype_of(code)
 
 
 def element_size_of(code: int) -> int:
     # activation element size (workspace sizing); dtype-4 weights are 1B
-    return {0: 4, 1: 4, 2: 2, 3: 2, 4: 2, 5: 2}[code]
+    return {0: 4, 1: 4, 2: 2, 3: 2, 4: 2, 5: 2, 6: 2}[code]
 
 
 # hidden_act enum (schema): 0 relu, 1 exact-erf gelu, 2 SwiGLU, 3 GeGLU.
@@ -214,5 +219,14 @@ def load_config(path: str | None = None) -> dict:
             f"hidden_act={cfg['hidden_act']} (gated) is not supported with "
             "torch_dtype=5 (MX fp8): the MX up epilogue cannot yet halve its "
             "output width")
+    if cfg["torch_dtype"] == 6:
+        if cfg["hidden_size"] % 128 or cfg["intermediate_size"] % 128:
+            raise ValueError(
+                f"torch_dtype=6 (MXFP4) needs hidden_size and intermediate_size "
+                f"to be multiples of 128; got {cfg['hidden_size']} and "
+                f"{cfg['intermediate_size']}")
+        if cfg["is_training"]:
+            raise ValueError("torch_dtype=6 (MXFP4) is not supported with "
+                             "is_training=1 (inference only)")
     _validate_router(cfg)
     return cfg

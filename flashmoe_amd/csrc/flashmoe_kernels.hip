@@ -3655,6 +3655,362 @@ void k_group_gemm_aqt(GemmArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Grouped GEMM, bf16 activations x MXFP4 weights (torch_dtype 6, W4A16;
+// DESIGN.md par.5p). B is e2m1, two elements per byte (even k in the low
+// nibble), with one E8M0 scale byte per 32 elements of K; the weights stay
+// packed through HBM and LDS and are dequantised at fragment read by
+// v_cvt_scalef32_pk_bf16_fp4, which applies 2^(s - 127) for free. e2m1 * 2^k
+// is exact in bf16, so this is a bf16 GEMM (v_mfma_f32_16x16x32_bf16, fp32
+// accumulation) on exactly dequantised weights.
+//
+// Tile: BM = 128, BK = 128, 512 threads = 2M x 4N waves, 3 stages, one block
+// per CU. BN = 128, or 256 for the gated up phase (128 output columns).
+//
+// A stage: [128 rows][256 B], 1 KiB DMA groups of 4 rows x 16 chunks of 16 B;
+//   the chunk at position p of row R holds source chunk p ^ (R & 15).
+// B stage: [BN rows][64 B], 1 KiB DMA groups of 16 rows x 4 chunks; the chunk
+//   at position p of row R holds source chunk p ^ ((R >> 2) & 3). A chunk is
+//   32 elements of K: exactly one MX block.
+// Scale stage: [BN rows][16 B]: the row's scale bytes of the aligned quad of
+//   K tiles around kb (one 16-byte DMA per row and stage, so every wave issues
+//   the same GPS loads per stage and one counted vmcnt wait serves all three).
+//   A window that would run past the end of the phase's scale part is moved
+//   back to end there; the reader adds the same shift.
+//
+// K order inside a tile: lane (rl, gk) reads B chunk gk whole (ONE 16-byte LDS
+// read per fragment and tile), whose dword d feeds MFMA step d. Step d of lane
+// gk therefore covers k = 32 gk + 8 d .. + 7, so the A fragment of step d is
+// chunk 4 gk + d, and all four steps of a lane use ONE scale, byte gk.
+//
+// Operands are swapped (weights first) as in aq_gemm_job_body: lane & 15 is
+// the output row, the four accumulator registers are output columns. Tile
+// row i = 4 q + r of B fragment j is sourced from weight row 8 q + 4 j + r of
+// the wave's 32 output columns, so that a lane's registers of the fragment
+// pair are EIGHT consecutive columns: one 16-byte store per row.
+// GATED: B fragments 0, 2 are Wglu rows, 1, 3 Wup rows (par.5f).
+// a.bScale carries the uint8 scales here: bScaleStride bytes per expert,
+// bScaleGlu bytes from s_up to s_glu; a.strideBExpert / gluOffset are bytes.
+// ---------------------------------------------------------------------------
+constexpr int W4_STAGES = 3;
+template <int BN> __host__ __device__ constexpr int w4_lds_bytes() {
+  return W4_STAGES * (128 * 256 + BN * 64 + BN * 16) + 128 * 8 + 128 * 4 + 16;
+}
+
+// one dword of e2m1 (8 elements of K, low nibble first) -> 8 bf16 times scale
+__device__ __forceinline__ bf16x8 dequant_fp4x8_bf16(uint32_t w, float scale) {
+  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+  const bf16x2v p0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0);
+  const bf16x2v p1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+  const bf16x2v p2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2);
+  const bf16x2v p3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+  return bf16x8{p0[0], p0[1], p1[0], p1[1], p2[0], p2[1], p3[0], p3[1]};
+}
+
+template <int PHASE, bool GATED, int BN>
+__device__ __forceinline__ void w4_gemm_job_body(const GemmArgs& a,
+                                                 char* smemBase, int e, int m0,
+                                                 int n0) {
+  static_assert(GATED ? (PHASE == 0 && BN == 256) : BN == 128,
+                "128 output columns per tile");
+  constexpr int BM = 128, BK = 128, SE = W4_STAGES;
+  constexpr int A_ST = BM * BK * 2, B_ST = BN * BK / 2, S_ST = BN * 16;
+  char* Abase = smemBase;                       // SE x [BM][256 B]
+  char* Bbase = Abase + SE * A_ST;              // SE x [BN][64 B]
+  char* Sbase = Bbase + SE * B_ST;              // SE x [BN][16 B]
+  TPS* sTps = reinterpret_cast<TPS*>(Sbase + SE * S_ST);
+  float* sScale = reinterpret_cast<float*>(sTps + BM);
+  uint32_t* sRouted = reinterpret_cast<uint32_t*>(sScale + BM);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int K = a.K, N = a.N;
+  const int nK = K / BK;
+  const int nOut = GATED ? (N >> 1) : N;  // weight rows per projection
+
+  const TPS* tpsE = a.tokenIds ? a.tokenIds + (size_t)e * a.pEC : nullptr;
+  __syncthreads();  // prior job's LDS readers done
+  if (tid == 0)
+    *sRouted = tpsE ? min(a.eC[e], (uint32_t)a.EC) : (uint32_t)a.nRows;
+  __syncthreads();
+  const uint32_t routed = *sRouted;
+  if ((uint32_t)m0 >= routed) return;
+  const int mCap = a.tokenIds ? a.pEC : a.nRows;
+  const int we = a.segExpert ? a.segExpert[e] : e;
+  // slot / scaled / nSlot: as in gemm_job_body
+  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
+  if (tid < BM) {
+    TPS t{0u, 1.0f};
+    if ((uint32_t)(m0 + tid) < routed)
+      t = tpsE ? tpsE[m0 + tid] : TPS{(uint32_t)(m0 + tid), 1.0f};
+    sTps[tid] = t;
+    if constexpr (PHASE == 1) {
+      float sc = 1.0f;
+      if (scaled && (uint32_t)(m0 + tid) < routed)
+        sc = toF(reinterpret_cast<const bf16*>(
+                 a.gate_out)[(size_t)tpsTok(t.tokenIdx) * a.PX +
+                             a.expertOffset + e]) / t.probSum;
+      sScale[tid] = sc;
+    }
+  }
+  __syncthreads();
+
+  const char* __restrict__ Ag = reinterpret_cast<const char*>(a.A);
+  const char* __restrict__ Bg =
+      reinterpret_cast<const char*>(a.B) + (size_t)we * a.strideBExpert;
+  const char* __restrict__ Sg =
+      reinterpret_cast<const char*>(a.bScale) + (size_t)we * a.bScaleStride;
+  const int nBase = GATED ? (n0 >> 1) : n0;
+  const int sPitch = K / 32;               // scale bytes per weight row
+  const int sLim = nOut * sPitch - 16;     // last window start inside a part
+
+  // tile-local B row -> weight row of its projection (clamped), and whether
+  // the row is a Wglu row
+  auto bRowOf = [&](int Rl, bool& glu) -> int {
+    const int wcR = Rl / (BN / 4);
+    const int ni = (Rl % (BN / 4)) >> 4;
+    const int i = Rl & 15;
+    const int j = GATED ? (ni >> 1) : ni;
+    glu = GATED && (ni & 1) == 0;
+    return min(nBase + wcR * 32 + 8 * (i >> 2) + 4 * j + (i & 3), nOut - 1);
+  };
+
+  constexpr int GPW_A = BM / 4 / 8;   // 1 KiB groups of 4 A rows, per wave
+  constexpr int GPW_B = BN / 16 / 8;  // 1 KiB groups of 16 B rows, per wave
+  constexpr int SRW = BN / 8;         // scale rows per wave
+  constexpr int GPS = GPW_A + GPW_B + 1;
+  const size_t aBase = (size_t)e * a.strideAExpert;  // elements
+  const char* aSrc[GPW_A];
+  const char* bSrc[GPW_B];
+#pragma unroll
+  for (int i = 0; i < GPW_A; ++i) {
+    const int row = (wave * GPW_A + i) * 4 + (lane >> 4);
+    const size_t grow = (PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
+                                     : (size_t)min(m0 + row, mCap - 1);
+    aSrc[i] = Ag + (aBase + grow * (size_t)K) * 2 +
+              (((lane & 15) ^ (row & 15)) * 16);
+  }
+#pragma unroll
+  for (int i = 0; i < GPW_B; ++i) {
+    const int Rl = (wave * GPW_B + i) * 16 + (lane >> 2);
+    bool glu;
+    const int prow = bRowOf(Rl, glu);
+    bSrc[i] = Bg + (glu ? a.gluOffset : 0) + (size_t)prow * (K / 2) +
+              (((lane & 3) ^ ((Rl >> 2) & 3)) * 16);
+  }
+  // scales: lanes < SRW of every wave, row wave * SRW + lane
+  const char* sSrc;
+  int sRowByte;
+  {
+    bool glu;
+    const int prow = bRowOf(wave * SRW + (lane & (SRW - 1)), glu);
+    sSrc = Sg + (glu ? a.bScaleGlu : 0);
+    sRowByte = prow * sPitch;
+  }
+  auto stage = [&](int kb, int buf) {
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(aSrc[i] + kb * (BK * 2)),
+          (las_u32*)(Abase + buf * A_ST + (wave * GPW_A + i) * 1024), 16, 0,
+          0);
+#pragma unroll
+    for (int i = 0; i < GPW_B; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(bSrc[i] + kb * (BK / 2)),
+          (las_u32*)(Bbase + buf * B_ST + (wave * GPW_B + i) * 1024), 16, 0,
+          0);
+    if (lane < SRW)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(sSrc + min(sRowByte + (kb & ~3) * 4, sLim)),
+          (las_u32*)(Sbase + buf * S_ST + wave * SRW * 16), 16, 0, 0);
+  };
+
+  const int wr = wave >> 2, wc = wave & 3;
+  constexpr int MI = BM / 32, NF = BN / 64;
+  f32x4 accv[MI][NF];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) accv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int rl = lane & 15;
+  const int gk = lane >> 4;
+  // this lane's B rows: LDS offsets of its chunk and of its scale window
+  int bOff[NF], sOff[NF], sRB[NF];
+#pragma unroll
+  for (int ni = 0; ni < NF; ++ni) {
+    const int Rl = wc * (BN / 4) + ni * 16 + rl;
+    bool glu;
+    sRB[ni] = bRowOf(Rl, glu) * sPitch;
+    bOff[ni] = Rl * 64 + ((gk ^ ((Rl >> 2) & 3)) * 16);
+    sOff[ni] = Rl * 16 + gk;
+  }
+
+  stage(0, 0);
+  if (nK > 1) {
+    stage(1, 1);
+    wait_vmcnt<GPS>();  // tile 0 landed; tile 1 in flight
+  } else {
+    wait_vmcnt<0>();
+  }
+  __builtin_amdgcn_s_barrier();
+  for (int t = 0; t < nK; ++t) {
+    const int pre = t + SE - 1;  // tile staged this iteration
+    const bool stageNow = pre < nK;
+    const char* Al = Abase + (t % SE) * A_ST;
+    const char* Bl = Bbase + (t % SE) * B_ST;
+    const uint8_t* Sl =
+        reinterpret_cast<const uint8_t*>(Sbase + (t % SE) * S_ST);
+    __builtin_amdgcn_s_setprio(1);
+    bf16x8 af[4][MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const int R = wr * (BM / 2) + mi * 16 + rl;  // R & 15 == rl
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        af[d][mi] = *reinterpret_cast<const bf16x8*>(
+            &Al[R * 256 + (((gk * 4 + d) ^ rl) * 16)]);
+    }
+    u32x4 bw[NF];
+    float bs[NF];
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni) {
+      bw[ni] = *reinterpret_cast<const u32x4*>(&Bl[bOff[ni]]);
+      // the window's shift, as stage() clamped it for this row
+      const int shift = max(sRB[ni] + (t & ~3) * 4 - sLim, 0);
+      const uint32_t sb = Sl[sOff[ni] + (t & 3) * 4 + shift];
+      bs[ni] = __uint_as_float(sb << 23);
+    }
+    // fragments are read BEFORE the next stage is issued (see
+    // aq_gemm_job_body: the compiler's own vmcnt(0) ahead of LDS reads)
+    if (stageNow) stage(pre, pre % SE);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      bf16x8 bq[NF];
+#pragma unroll
+      for (int ni = 0; ni < NF; ++ni)
+        bq[ni] = dequant_fp4x8_bf16(bw[ni][d], bs[ni]);
+#pragma unroll
+      for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+          accv[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              bq[ni], af[d][mi], accv[mi][ni], 0, 0, 0);
+    }
+    __builtin_amdgcn_s_setprio(0);
+    if (stageNow) wait_vmcnt<GPS>(); else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+  }
+
+  // epilogue: lane & 15 is the row of fragment mi; the lane's registers of
+  // output fragments 0 and 1 are columns oBase .. oBase + 7
+  const int act = a.act;
+  const int oBase = nBase + wc * 32 + 8 * gk;
+  float bv[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) bv[c] = 0.f;
+  if (a.bias) {
+    const bf16* bptr = reinterpret_cast<const bf16*>(a.bias) +
+                       (a.strideBExpert ? (size_t)we * nOut : 0);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (oBase + c < nOut) bv[c] = toF(bptr[oBase + c]);
+  }
+  bf16* outBase;
+  if constexpr (PHASE == 1)
+    outBase = reinterpret_cast<bf16*>(slot ? (void*)a.O32 : a.moe_out);
+  else
+    outBase = reinterpret_cast<bf16*>(a.out) + (size_t)e * a.strideOExpert;
+  const long long rowPitch = (PHASE == 1) ? a.H : nOut;
+  const bool wideOK = (rowPitch & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(outBase) & 15) == 0;
+  const bool vecOK = (rowPitch & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(outBase) & 7) == 0;
+  const int nValid = nOut - oBase;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int row = wr * (BM / 2) + mi * 16 + rl;
+    const int m = m0 + row;
+    if ((uint32_t)m >= routed || nValid <= 0) continue;  // not written
+    bf16* orow;
+    float rowScale = 1.0f;
+    if constexpr (PHASE == 1) {
+      const TPS tp = sTps[row];
+      if (slot) {
+        orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
+                          tpsJ(tp.tokenIdx)) * rowPitch;
+        rowScale = sScale[row];
+      } else {
+        orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+      }
+    } else {
+      orow = outBase + (size_t)m * rowPitch;
+    }
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x;
+        if constexpr (GATED) {
+          x = gate_act(accv[mi][2 * j][r], act) * accv[mi][2 * j + 1][r];
+        } else {
+          x = accv[mi][j][r] + bv[4 * j + r];
+          if constexpr (PHASE == 0)
+            x = (act == 0)
+                ? fmaxf(x, 0.0f)
+                : 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+          if constexpr (PHASE == 1)
+            if (slot) x = x * rowScale;
+        }
+        v[4 * j + r] = x;
+      }
+    if (wideOK) {
+      const uint32_t w[4] = {
+          ETr<bf16>::pack2(v[0], v[1]), ETr<bf16>::pack2(v[2], v[3]),
+          ETr<bf16>::pack2(v[4], v[5]), ETr<bf16>::pack2(v[6], v[7])};
+      storeRow8(orow + oBase, w, nValid);
+    } else {
+      const float lo[4] = {v[0], v[1], v[2], v[3]};
+      const float hi[4] = {v[4], v[5], v[6], v[7]};
+      storeRow4<false>(orow + oBase, lo, nValid, vecOK);
+      if (nValid > 4) storeRow4<false>(orow + oBase + 4, hi, nValid - 4, vecOK);
+    }
+  }
+}
+
+// 3 stages: BN = 128 takes 127.5 KiB of LDS, BN = 256 157.5 KiB: one block of
+// eight waves per CU either way (two stages of the 32 KiB bf16 A tile alone
+// leave no room for a second block).
+template <int PHASE, bool GATED, int BN>
+__global__ __launch_bounds__(512, 1) FM_NO_PK_F32
+void k_group_gemm_w4(GemmArgs a) {
+  constexpr int BM = 128;
+  __shared__ __attribute__((aligned(16))) char smem[w4_lds_bytes<BN>()];
+  const int mT = a.totalJobs > 0 ? a.jobsMT : gridDim.x;
+  const int nT = a.totalJobs > 0 ? a.jobsNT : gridDim.y;
+  const int gstride = gridDim.x * gridDim.y * gridDim.z;
+  const int nBlocks = a.totalJobs > 0 ? a.totalJobs : gstride;
+  const int lin0 =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int qx = nBlocks / 8, rx = nBlocks % 8;
+  for (int jl = lin0; jl < nBlocks; jl += gstride) {
+    const int xcd = jl % 8, pos = jl / 8;
+    const int swz = a.noRemap
+        ? jl
+        : (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+    const int e = swz / (mT * nT);
+    const int rem = swz % (mT * nT);
+    w4_gemm_job_body<PHASE, GATED, BN>(a, smem, e, (rem % mT) * BM,
+                                       (rem / mT) * BN);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fp32 grouped GEMM (config-1 "CPU correctness plumbing" shapes; VALU
 // tiled). 64x64 tile, 256 threads, each thread a 4x4 sub-block, BK=16.
 // Same phase semantics as the bf16 kernel.
@@ -4982,6 +5338,8 @@ __global__ __launch_bounds__(512, 1) void k_moe_fused(GemmArgs gl, GemmArgs gu,
 
 static int launch_group_gemm(hipStream_t st, int phase, const struct GemmArgs& a,
                              int M, int nE);
+static int launch_group_gemm_w4(hipStream_t st, int phase,
+                                const struct GemmArgs& a, int M, int nE);
 static int launch_quant_g128(hipStream_t st, const void* in, uint8_t* out,
                              uint8_t* scales, long long nRows, int K,
                              int sPitch = 0);
@@ -5073,10 +5431,21 @@ struct State {
   // record = [s_up (PB x HB) | s_dn (HB x PB) | s_glu (PB x HB)]. At most one
   // of wScale / bScale is set.
   const float* bScale = nullptr;
-  int wScaleGran = 0;        // 0 none, 1 per output channel, 2 per block
+  // or, for MXFP4 weights (torch_dtype 6, fm_set_weight_mx_scales, DESIGN.md
+  // par.5p), one E8M0 byte per 32 elements of K: borrowed device tensor
+  // [nLx + nSh, (2 or 3) * P * H / 32], record = [s_up (P x H/32) |
+  // s_dn (H x P/32) | s_glu (P x H/32)]
+  const uint8_t* mxScale = nullptr;
+  int wScaleGran = 0;        // 0 none, 1 per output channel, 2 per block,
+                             // 3 MX (per 32 of K)
   uint32_t wScaleGen = 0;    // bumped per set call: part of the graph key
 };
 State g;
+
+// bytes of n expert-weight elements (two e2m1 elements per byte for dtype 6)
+static size_t wBytes(size_t n) {
+  return g.cfg.dtype == 6 ? n / 2 : n * g.wesz;
+}
 
 // The same for block scales: the phase's grid [N/128][K/128] inside the
 // record of weight expert `firstExpert`. Null without block scales.
@@ -5105,6 +5474,16 @@ static void setWeightScaleArgs(GemmArgs& a, int phase, int firstExpert,
   a.wScaleStride = strided ? SC : 0;
   a.wScaleGlu = g.P + g.H;  // s_up -> s_glu inside a record (gated up phase)
   setBlockScaleArgs(a, phase, firstExpert, strided);
+  if (g.cfg.dtype == 6) {
+    // MX scales ride the bScale fields as bytes (k_group_gemm_w4)
+    const long long part = (long long)g.P * g.H / 32;
+    const long long MXSC = (g.gated ? 3 : 2) * part;
+    a.bScale = reinterpret_cast<const float*>(
+        g.mxScale + (size_t)firstExpert * MXSC + (phase == 0 ? 0 : part));
+    a.bScaleStride = strided ? MXSC : 0;
+    a.bScaleKB = (phase == 0 ? g.H : g.P) / 32;
+    a.bScaleGlu = (int)(2 * part);  // s_up -> s_glu (gated up phase)
+  }
 }
 
 // kernel-side view of g.router
@@ -5136,6 +5515,15 @@ void setErr(const char* msg) {
       return FM_ERR_HIP;                                                     \
     }                                                                        \
   } while (0)
+
+// dtype 6 cannot run without its scales: every entry point that launches an
+// expert GEMM refuses first
+static bool mxScalesMissing() {
+  if (g.cfg.dtype != 6 || g.mxScale) return false;
+  setErr("torch_dtype 6 (MXFP4) has no weight scales attached: call "
+         "fm_set_weight_mx_scales before a forward or an expert FFN");
+  return true;
+}
 
 // dtype 5: does the MX grouped GEMM pick the 256^2 tile for (M, N)?
 // (mirrored by launch_group_gemm's MX branch; the 256-tile up epilogue
@@ -5310,7 +5698,8 @@ int launch_gate(hipStream_t st, const void* x, const void* gate_w,
     int rc = launch_group_gemm(st, 3, ga, (int)S, 1);
     if (rc != FM_OK) return rc;
   }
-  if (g.cfg.dtype == 2 || g.cfg.dtype == 4 || g.cfg.dtype == 5) {
+  if (g.cfg.dtype == 2 || g.cfg.dtype == 4 || g.cfg.dtype == 5 ||
+      g.cfg.dtype == 6) {
     if (!mfmaLogits) GATE_LOGITS(bf16);
     GATE_K(bf16)
   } else if (g.cfg.dtype == 3) {
@@ -5654,6 +6043,7 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
   g.routerRV = false;
   g.wScale = nullptr;  // and without weight scales
   g.bScale = nullptr;
+  g.mxScale = nullptr;
   g.wScaleGran = 0;
   g.actQuant = 0;  // and with bf16 activations
   g.cfg = *cfg;
@@ -5678,16 +6068,32 @@ int fm_initialize(const fm_config* cfg, int rank, int world_size) {
     case 4: g.esz = 2; break;  // fp8e4m3 expert weights, bf16 activations
     case 5: g.esz = 2; break;  // MX: fp8 weights + runtime-quantized
                                // fp8 activations on the scaled MFMA
+    case 6: g.esz = 2; break;  // MXFP4 expert weights (e2m1 + E8M0 per 32),
+                               // bf16 activations (par.5p)
     default: setErr("unknown dtype");
              return FM_ERR_UNSUPPORTED;
   }
-  g.wesz = (cfg->dtype == 4 || cfg->dtype == 5) ? 1 : g.esz;
+  g.wesz = (cfg->dtype == 4 || cfg->dtype == 5 || cfg->dtype == 6)
+               ? 1 : g.esz;  // dtype 6: half a byte, see wBytes()
   if (cfg->hidden_act < 0 || cfg->hidden_act > 3) {
     setErr("hidden_act must be 0 (relu), 1 (gelu), 2 (swiglu) or 3 (geglu)");
     return FM_ERR_UNSUPPORTED;
   }
   g.gated = cfg->hidden_act >= 2;
   g.wMats = g.gated ? 3 : 2;
+  if (cfg->dtype == 6 &&
+      (cfg->hidden_size % 128 || cfg->intermediate_size % 128)) {
+    snprintf(g_err, sizeof(g_err),
+             "torch_dtype 6 (MXFP4) needs hidden_size and intermediate_size "
+             "to be multiples of 128; got hidden_size %d, intermediate_size "
+             "%d", (int)cfg->hidden_size, (int)cfg->intermediate_size);
+    return FM_ERR_UNSUPPORTED;
+  }
+  if (cfg->dtype == 6 && cfg->is_training) {
+    setErr("torch_dtype 6 (MXFP4) is not supported with is_training 1 "
+           "(inference only)");
+    return FM_ERR_UNSUPPORTED;
+  }
   // shared experts: refused loudly where they cannot run (checked ahead of
   // the gated + MX refusal so the message names the key that asked)
   g.nSh = cfg->num_shared_experts;
@@ -6030,6 +6436,7 @@ int fm_set_weight_scales(const float* scales, int32_t granularity) {
   }
   g.wScale = granularity == 1 ? scales : nullptr;
   g.bScale = nullptr;  // one kind of scale at a time
+  g.mxScale = nullptr;
   g.wScaleGran = granularity;
   ++g.wScaleGen;  // never replay a forward captured under other scales
   return FM_OK;
@@ -6061,7 +6468,24 @@ int fm_set_weight_block_scales(const float* scales) {
   }
   g.bScale = scales;
   g.wScale = nullptr;  // one kind of scale at a time
+  g.mxScale = nullptr;
   g.wScaleGran = scales ? 2 : 0;
+  ++g.wScaleGen;  // never replay a forward captured under other scales
+  return FM_OK;
+}
+
+int fm_set_weight_mx_scales(const uint8_t* scales) {
+  if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
+  if (scales && g.cfg.dtype != 6) {
+    snprintf(g_err, sizeof(g_err),
+             "weight mx scales need MXFP4 expert weights: torch_dtype must be "
+             "6, the config has torch_dtype %d", (int)g.cfg.dtype);
+    return FM_ERR_UNSUPPORTED;
+  }
+  g.mxScale = scales;
+  g.wScale = nullptr;  // one kind of scale at a time
+  g.bScale = nullptr;
+  g.wScaleGran = scales ? 3 : 0;
   ++g.wScaleGen;  // never replay a forward captured under other scales
   return FM_OK;
 }
@@ -6181,7 +6605,9 @@ int fm_quant_fp8_row_counted(void* stream, const void* in, void* out8,
 
 int fm_get_weight_scales(const float** scales, int32_t* granularity) {
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
-  if (scales) *scales = g.bScale ? g.bScale : g.wScale;
+  if (scales)
+    *scales = g.mxScale ? reinterpret_cast<const float*>(g.mxScale)
+              : g.bScale ? g.bScale : g.wScale;
   if (granularity) *granularity = g.wScaleGran;
   return FM_OK;
 }
@@ -6195,6 +6621,9 @@ int fm_get_router(fm_router_config* out) {
 
 static int launch_group_gemm(hipStream_t st, int phase, const GemmArgs& a,
                              int M, int nE) {
+  // MXFP4 weights: one kernel family, ahead of every tile-mode choice
+  if (g.cfg.dtype == 6 && phase != 3)
+    return launch_group_gemm_w4(st, phase, a, M, nE);
   const int act = (phase == 0) ? a.act : 0;
   // gated up phase (hidden_act 2/3; never dtype 5, fm_initialize refuses
   // it): the callers describe the plain [P, H] problem; the kernels run
@@ -6570,7 +6999,8 @@ static int decodeFfnMode() {
 // does a forward take k_decode_ffn? Only below 128 tokens, and only for the
 // 2-byte activation families (fp32 stays on k_group_gemm_f32).
 static bool decodeFfnApplies() {
-  if (g.S >= 128 || g.esz != 2 || g.cfg.dtype == 5) return false;
+  if (g.S >= 128 || g.esz != 2 || g.cfg.dtype == 5 || g.cfg.dtype == 6)
+    return false;  // (no fp4 weight-streaming kernel: par.5p, open items)
   const int m = decodeFfnMode();
   if (m >= 0) return m == 1;
   return g.S <= (g.cfg.dtype == 4   ? kDecodeFfnMaxSFp8
@@ -6812,6 +7242,48 @@ static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
   return FM_OK;
 }
 
+// torch_dtype 6 (par.5p): k_group_gemm_w4 on the aq launch's walk (grid per
+// tile, persistent beyond one block per CU). The caller describes the plain
+// problem in weight ELEMENTS; the kernel takes bytes of the packed layout.
+static int launch_group_gemm_w4(hipStream_t st, int phase, const GemmArgs& a,
+                                int M, int nE) {
+  const bool gated = phase == 0 && a.act >= 2;
+  if (gated && a.bias) {
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  GemmArgs aa = a;
+  aa.N = gated ? 2 * a.N : a.N;
+  aa.strideBExpert = a.strideBExpert / 2;
+  aa.gluOffset = gated ? (long long)a.N * a.K : 0;  // slot 0 -> slot 2, bytes
+  aa.splitK = 1;
+  aa.noRemap = 0;
+  aa.totalJobs = 0;
+  const int nCU = g.nCU > 0 ? g.nCU : 256;
+  dim3 grid(DIVUP(M, 128), DIVUP(aa.N, gated ? 256 : 128), nE);
+  const int J = grid.x * grid.y * nE;
+  if (J > nCU) {  // one block per CU by LDS
+    aa.totalJobs = J;
+    aa.jobsMT = grid.x;
+    aa.jobsNT = grid.y;
+    grid = dim3(nCU, 1, 1);
+  }
+  if (gated)
+    hipLaunchKernelGGL((k_group_gemm_w4<0, true, 256>), grid, dim3(512), 0, st,
+                       aa);
+  else if (phase == 0)
+    hipLaunchKernelGGL((k_group_gemm_w4<0, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  else if (phase == 1)
+    hipLaunchKernelGGL((k_group_gemm_w4<1, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  else
+    hipLaunchKernelGGL((k_group_gemm_w4<2, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
 static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
                             const void* expert_w, const void* b_up,
                             const void* b_dn, void* gate_out, void* moe_out,
@@ -6836,7 +7308,8 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   // it runs the e4m3 x e4m3 GEMMs, whatever FM_FUSED says)
   const bool aq = g.actQuant != 0;
   if (fusedEnabled() && g.S >= 128 && g.esz == 2 && g.world == 1 &&
-      g.cfg.dtype != 5 && !g.gated && g.nSh == 0 && !g.routerRV &&
+      g.cfg.dtype != 5 && g.cfg.dtype != 6 && !g.gated && g.nSh == 0 &&
+      !g.routerRV &&
       !g.wScale && !g.bScale && !aq) {
     int rc = moe_forward_fused(st, x, gate_w, expert_w, b_up, b_dn, gate_out,
                                moe_out);
@@ -6938,7 +7411,7 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
   dn.outScales = nullptr;
   dn.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.xM8 : g.xM;
   dn.aScales = g.xMs;
-  dn.B = reinterpret_cast<const char*>(expert_w) + (size_t)g.P * g.H * g.wesz;
+  dn.B = reinterpret_cast<const char*>(expert_w) + wBytes((size_t)g.P * g.H);
   dn.bias = b_dn;
   dn.out = nullptr;
   dn.O32 = reinterpret_cast<float*>(g.cbuf);  // non-atomic combine slots
@@ -6968,6 +7441,7 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
     return FM_ERR_STATE;
   }
   if (S != g.S) { setErr("S mismatch vs frozen config"); return FM_ERR_SHAPE; }
+  if (mxScalesMissing()) return FM_ERR_STATE;
   int prc = fusedPoisonCheck();  // a prior fused forward that gave up
   if (prc != FM_OK) return prc;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -6985,7 +7459,8 @@ int fm_moe_forward(void* stream, const void* x, const void* gate_w,
                       (uint64_t)(decodeFfnMode() + 1) << 38 |
                       (uint64_t)S << 2 | (gateFusedEnabled() ? 2 : 0) |
                       (fusedEnabled() ? 1 : 0))),
-                  const_cast<float*>(g.bScale ? g.bScale : g.wScale),
+                  g.mxScale ? (void*)const_cast<uint8_t*>(g.mxScale)
+                      : const_cast<float*>(g.bScale ? g.bScale : g.wScale),
                   reinterpret_cast<void*>(static_cast<uintptr_t>(
                       (uint64_t)g.actQuant << 32 | g.wScaleGen))};
   if (g.graphValid && memcmp(key, g.graphKey, sizeof(key)) == 0) {
@@ -7033,6 +7508,7 @@ int fm_moe_forward_phased(void* stream, const void* x, const void* gate_w,
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
   if (g.world != 1) { setErr("single-rank path only"); return FM_ERR_STATE; }
   if (S != g.S) { setErr("S mismatch vs frozen config"); return FM_ERR_SHAPE; }
+  if (mxScalesMissing()) return FM_ERR_STATE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   hipEvent_t evs[6];
   for (auto& e : evs) FM_HIP_CHECK(hipEventCreate(&e));
@@ -7118,6 +7594,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
     setErr("dtype 5 (MX fp8) supports fm_moe_forward only this round");
     return FM_ERR_UNSUPPORTED;
   }
+  if (mxScalesMissing()) return FM_ERR_STATE;
   if (n_rows <= 0) return FM_OK;
   if (n_rows > (int64_t)g.nLxAlloc * g.pEC) {
     setErr("n_rows exceeds workspace"); return FM_ERR_SHAPE;
@@ -7126,7 +7603,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   GemmArgs up{};
   up.A = rows;
   up.B = reinterpret_cast<const char*>(expert_w) +
-         (size_t)local_e * g.wMats * g.P * g.H * g.wesz;
+         wBytes((size_t)local_e * g.wMats * g.P * g.H);
   up.bias = b_up;
   up.out = g.xM;  // scratch [n_rows, P]
   up.tokenIds = nullptr; up.eC = nullptr;
@@ -7154,7 +7631,7 @@ int fm_expert_ffn(void* stream, const void* rows, const void* expert_w,
   GemmArgs dn = up;
   dn.A = g.xM;
   dn.B = reinterpret_cast<const char*>(expert_w) +
-         ((size_t)local_e * g.wMats + 1) * g.P * g.H * g.wesz;
+         wBytes(((size_t)local_e * g.wMats + 1) * g.P * g.H);
   dn.bias = b_dn;
   dn.out = out_rows;
   dn.K = g.P; dn.N = g.H;
@@ -7390,6 +7867,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   if ((int64_t)n_segs * g.EC > (int64_t)g.nLxAlloc * g.pEC) {
     setErr("segments exceed xM workspace"); return FM_ERR_SHAPE;
   }
+  if (mxScalesMissing()) return FM_ERR_STATE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (g.cfg.dtype == 5) {
     // MX: quantize the received rows once; the MX GEMM reads x8/scales
@@ -7451,7 +7929,7 @@ int fm_expert_ffn_segments(void* stream, const void* rows,
   dn.outScales = nullptr;
   dn.A = (g.cfg.dtype == 5 || aq) ? (const void*)g.xM8 : g.xM;
   dn.aScales = g.xMs;
-  dn.B = reinterpret_cast<const char*>(expert_w) + (size_t)g.P * g.H * g.wesz;
+  dn.B = reinterpret_cast<const char*>(expert_w) + wBytes((size_t)g.P * g.H);
   dn.out = out_rows;
   dn.strideAExpert = (long long)g.EC * g.P;
   dn.strideOExpert = (long long)g.EC * g.H;

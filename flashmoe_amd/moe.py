@@ -269,6 +269,80 @@ def set_weight_block_scales(scales):
     _state["weight_scales"] = scales
 
 
+def _weight_mx_scale_shape():
+    """(records, MXSC) of the MX scale tensor for the initialized config: one
+    record [s_up (P x H/32) | s_dn (H x P/32) | s_glu (P x H/32, gated only)]
+    per local routed expert, then one per shared expert."""
+    cfg = _state["cfg"]
+    part = cfg["intermediate_size"] * cfg["hidden_size"] // 32
+    n = _ext.load().fm_get_num_local_experts() + num_shared(cfg)
+    return n, expert_mats(cfg["hidden_act"]) * part
+
+
+def set_weight_mx_scales(scales):
+    """Attach (or, with None, detach) the E8M0 scales of MXFP4 expert weights
+    (torch_dtype 6): W_eff[r, c] = e2m1(nibble[r, c]) * 2^(s[r][c // 32] - 127)
+    (DESIGN.md par.5p). `scales` is a contiguous uint8 CUDA tensor
+    [nLx + nSh, MXSC] as built by pack_weight_mx_scales, bytes in 1..254 (not
+    checked). The tensor is borrowed by the library and kept alive here; its
+    contents may be rewritten in place between forwards."""
+    import torch
+
+    if not _state["initialized"]:
+        raise RuntimeError("Must call initialize() first")
+    lib = _ext.load()
+    if scales is None:
+        _ext.check(lib.fm_set_weight_mx_scales(None), "fm_set_weight_mx_scales")
+        _state["weight_scales"] = None
+        return
+    dt = _state["cfg"]["torch_dtype"]
+    if dt != 6:
+        raise ValueError(
+            f"weight mx scales need MXFP4 expert weights (torch_dtype 6); the "
+            f"initialized config has torch_dtype {dt}")
+    want = _weight_mx_scale_shape()
+    if not isinstance(scales, torch.Tensor) or not scales.is_cuda or \
+            scales.dtype != torch.uint8 or tuple(scales.shape) != want or \
+            not scales.is_contiguous():
+        got = (f"{scales.dtype} {list(scales.shape)} on {scales.device}"
+               if isinstance(scales, torch.Tensor) else type(scales).__name__)
+        raise ValueError(
+            f"weight mx scales must be a contiguous CUDA uint8 tensor of "
+            f"shape [nLx + nSh, MXSC] = {list(want)}; got {got}")
+    _ext.check(lib.fm_set_weight_mx_scales(ctypes.c_void_p(scales.data_ptr())),
+               "fm_set_weight_mx_scales")
+    _state["weight_scales"] = scales
+
+
+def pack_weight_mx_scales(up, down, glu=None):
+    """Build the [nE, MXSC] uint8 MX scale tensor from per-matrix E8M0 grids:
+    `up` [nE, P, H/32] (Wup [P, H]), `down` [nE, H, P/32] (the down buffer
+    used as [H, P]) and, for gated experts, `glu` [nE, P, H/32]; each grid is
+    [output channel, K block of 32]. nE counts the shared experts, which come
+    last. Returns a contiguous uint8 tensor on the device of `up`, with
+    records [s_up | s_dn | s_glu]."""
+    import torch
+
+    named = [("up", up), ("down", down)] + ([("glu", glu)] if glu is not None
+                                            else [])
+    parts = [(n, torch.as_tensor(t)) for n, t in named]
+    for name, t in parts:
+        if t.dim() != 3 or t.dtype != torch.uint8:
+            raise ValueError(
+                f"{name} mx scales must be uint8 [nE, output channels, K / "
+                f"32]; got {t.dtype} {list(t.shape)}")
+    nE, P, HB = parts[0][1].shape
+    for name, t in parts[1:]:
+        want = (nE, HB * 32, P // 32) if name == "down" else (nE, P, HB)
+        if P % 32 or tuple(t.shape) != want:
+            raise ValueError(
+                f"pack_weight_mx_scales: {name} must be {list(want)} beside "
+                f"up {list(parts[0][1].shape)}; got {list(t.shape)}")
+    dev = parts[0][1].device
+    return torch.cat([t.to(dev).reshape(nE, -1) for _, t in parts],
+                     dim=1).contiguous()
+
+
 ACTIVATION_QUANT_MODES = {None: 0, "group128": 1, "token": 2}
 
 
@@ -338,7 +412,8 @@ def get_weight_scales():
         raise RuntimeError(
             f"weight scales at {ptr.value or 0:#x} (granularity {gran.value}) "
             f"were attached through fm_set_weight_scales / "
-            f"fm_set_weight_block_scales directly, not through this module: "
+            f"fm_set_weight_block_scales / fm_set_weight_mx_scales directly, "
+            f"not through this module: "
             f"there is no tensor to return")
     return t
 
@@ -530,7 +605,13 @@ def _validate_forward_args(input, gate_weights, expert_weights):
                 f"[nLx, 3, P, H] for the gated hidden_act={act}. Got dim 1 = "
                 f"{expert_weights.size(1)}")
         raise ValueError("Expert weights must have up and down projections [nLx, 2, P, H]")
-    if expert_weights.size(2) != P or expert_weights.size(3) != H:
+    if _state["cfg"]["torch_dtype"] == 6:  # two e2m1 elements per byte
+        if expert_weights.size(2) != P or expert_weights.size(3) != H // 2:
+            raise ValueError(
+                f"MXFP4 expert weights must be [*, {nm}, P={P}, H/2={H // 2}]"
+                f". Got [*, {nm}, {expert_weights.size(2)}, "
+                f"{expert_weights.size(3)}]")
+    elif expert_weights.size(2) != P or expert_weights.size(3) != H:
         raise ValueError(
             f"Expert weights must be [*, {nm}, P={P}, H={H}]. Got "
             f"[*, {nm}, {expert_weights.size(2)}, {expert_weights.size(3)}]"
@@ -549,7 +630,8 @@ _KEEP = object()  # moe_forward(activation_quant=...): leave the mode as it is
 
 
 def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
-                weight_block_scales=None, activation_quant=_KEEP):
+                weight_block_scales=None, activation_quant=_KEEP,
+                weight_mx_scales=None):
     """Mirror of _C.moe_forward (python_bindings.cu:17-151): one DMoE
     forward on this rank's tokens. Single-rank path; world>1 uses the EP
     pipeline in ep.py (same result per rank). With
@@ -561,7 +643,8 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
     (torch_dtype 4): the same for set_weight_block_scales; pass one kind.
     activation_quant: "group128", "token" or None sets that mode first
     (set_activation_quant) when it is not the active one; left out, the mode
-    stays as it is."""
+    stays as it is. weight_mx_scales (torch_dtype 6): the same for
+    set_weight_mx_scales."""
     import torch
 
     S, H, E, P, nLx = _validate_forward_args(input, gate_weights, expert_weights)
@@ -577,6 +660,12 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
                              "both: one kind of scale is attached at a time")
         if weight_block_scales is not _state["weight_scales"]:
             set_weight_block_scales(weight_block_scales)
+    if weight_mx_scales is not None:
+        if weight_scales is not None or weight_block_scales is not None:
+            raise ValueError("pass one kind of weight scales: one kind is "
+                             "attached at a time")
+        if weight_mx_scales is not _state["weight_scales"]:
+            set_weight_mx_scales(weight_mx_scales)
     if _state["world"] != 1:
         from . import ep
 

@@ -233,6 +233,47 @@ int fm_get_weight_scales(const float** scales, int32_t* granularity);
  * tensor while activation quant mode 2 (token) is active (nothing changes). */
 int fm_set_weight_block_scales(const float* scales);
 
+/* MXFP4 expert weights (dtype 6, W4A16): what gpt-oss ships
+ * and the weight half of the Quark MXFP4 checkpoints. Activations (x, gate_w,
+ * biases, gate_out, moe_out, the intermediate) are bf16 exactly as for dtype
+ * 4, the gate is untouched.
+ * expert_w: uint8 [nLx + nSh, mats, P, H/2] (mats 2 or 3, the usual slot
+ * order): slots 0 and 2 are [P, H/2], slot 1 is the flat down buffer used as
+ * [H, P/2]. Element k of a row lives in byte k/2, even k in the LOW nibble.
+ * Nibble codes are OCP e2m1: magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6, bit 3 the
+ * sign.
+ * scales: device uint8 (E8M0), contiguous [nLx + nSh, MXSC], MXSC =
+ * mats * P * H / 32; an expert's record is [s_up (P x H/32) | s_dn (H x P/32)
+ * | s_glu (P x H/32)], each part row-major [output channel, K block of 32];
+ * the shared experts' records trail the routed ones.
+ *   W_eff[r, c] = e2m1(nibble[r, c]) * 2^(s[r][c / 32] - 127)
+ *   acc[m, n]   = sum_k bf16(x[m, k]) * W_eff[n, k]        (fp32)
+ * W_eff is exact in bf16, so the GEMMs are bf16 GEMMs on exactly dequantised
+ * weights; bias, activation, gating, the one bf16 rounding of the
+ * intermediate, the combine and the shared slices are those of dtype 4
+ * without scales. No atomics: two forwards are bit-identical. Scale bytes must
+ * lie in 1..254; the contents are NOT checked.
+ * Lifetime as fm_set_weight_scales: BORROWED until the next set call of any
+ * kind or fm_finalize, rewritable in place between forwards, reset by
+ * fm_initialize / fm_finalize; a set call invalidates the captured forward
+ * graph; NULL detaches. While attached fm_get_weight_scales reports
+ * granularity 3 and this pointer.
+ * Read by fm_moe_forward, fm_moe_forward_phased, fm_expert_ffn,
+ * fm_expert_ffn_segments and fm_expert_ffn_grouped, at S >= 128 and at
+ * S in 1..127 (the masked 128-row tile). A dtype-6 forward always runs
+ * k_group_gemm_w4: never k_moe_fused or k_decode_ffn, whatever FM_FUSED or
+ * FM_DECODE_FFN say, and FM_FORCE_MODE does not apply. Those entry points
+ * return FM_ERR_STATE (the message names fm_set_weight_mx_scales) on dtype 6
+ * while no scales are attached.
+ * dtype 6 itself is refused by fm_initialize (FM_ERR_UNSUPPORTED) when
+ * hidden_size or intermediate_size is not a multiple of 128 or with
+ * is_training 1; fm_set_weight_scales(granularity 1),
+ * fm_set_weight_block_scales and a non-zero fm_set_activation_quant are
+ * refused on dtype 6.
+ * FM_ERR_UNSUPPORTED (the message names the cause): a non-null tensor with a
+ * torch_dtype other than 6 (nothing changes). */
+int fm_set_weight_mx_scales(const uint8_t* scales);
+
 /* fp8 activations for the fp8 expert weights (dtype 4 only; DESIGN.md
  * par.5n): what the W8A8 FP8 checkpoints prescribe (activation_scheme
  * dynamic, weight_block_size [128, 128]). mode 0: off, bf16 activations (the

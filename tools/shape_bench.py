@@ -36,7 +36,10 @@ multiples of 128) sets set_activation_quant("group128"), or with the word
 token set_activation_quant("token") (par.5o; not with --weight-block-scales):
 fp8 activations and
 the e4m3 x e4m3 expert GEMMs; it composes with both weight-scale flags,
---hidden-act and --shared.
+--hidden-act and --shared. dtype 6 (MXFP4 expert weights, DESIGN.md par.5p;
+H and P multiples of 128) draws uniform nibbles and E8M0 scale bytes in
+121..130 and attaches them with set_weight_mx_scales; its weight_bytes count
+the packed nibbles and the scales.
 """
 import ctypes
 import json
@@ -130,8 +133,18 @@ if router:
 score_bias = None
 if router in ("v3", "sigmoid"):
     score_bias = 0.1 * torch.randn(E, dtype=torch.float32, device="cuda")
-ew_all = torch.randn(E + n_shared + n_compose, expert_mats(hidden_act), P, H,
-                     dtype=torch.float32, device="cuda").to(wdt)
+mx_scales = None
+if dtype_code == 6:
+    gen6 = torch.Generator(device="cuda").manual_seed(48)
+    ew_all = torch.randint(
+        0, 256, (E + n_shared + n_compose, expert_mats(hidden_act), P, H // 2),
+        dtype=torch.uint8, device="cuda", generator=gen6)
+    mx_scales = torch.randint(
+        121, 131, (E + n_shared, expert_mats(hidden_act) * P * H // 32),
+        dtype=torch.uint8, device="cuda", generator=gen6)
+else:
+    ew_all = torch.randn(E + n_shared + n_compose, expert_mats(hidden_act), P,
+                         H, dtype=torch.float32, device="cuda").to(wdt)
 ew = ew_all[:E + n_shared]  # what moe_forward sees (a leading slice)
 w_scales = None
 if weight_scales:
@@ -176,6 +189,8 @@ def measure(S):
         moe.set_weight_scales(w_scales)
     if activation_quant:
         moe.set_activation_quant(activation_quant)
+    if mx_scales is not None:
+        moe.set_weight_mx_scales(mx_scales)
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
     x = x.view(cfg["mini_batch"], cfg["sequence_len"], H)
@@ -250,6 +265,8 @@ def measure(S):
     hit = int((counts > 0).sum())
     weight_bytes = ((hit + n_shared) * expert_mats(hidden_act) * P * H *
                     ew.element_size())
+    if dtype_code == 6:  # half a byte per element, one scale byte per 32
+        weight_bytes = weight_bytes // 2 + weight_bytes // 32
     flops = 4.0 * S * topk * H * P  # upper bound (pre-capacity-drop)
     gemm_ms = acc[1] + acc[2]
     res = {
