@@ -77,6 +77,10 @@ def _bind(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.fm_quant_fp8_row.restype = ctypes.c_int
     lib.fm_quant_fp8_row_counted.argtypes = [p, p, p, p, p, i64, i64, i64, i64]
     lib.fm_quant_fp8_row_counted.restype = ctypes.c_int
+    lib.fm_quant_mxfp8.argtypes = [p, p, p, p, i64, i64]
+    lib.fm_quant_mxfp8.restype = ctypes.c_int
+    lib.fm_quant_mxfp8_counted.argtypes = [p, p, p, p, p, i64, i64, i64, i64]
+    lib.fm_quant_mxfp8_counted.restype = ctypes.c_int
     lib.fm_get_weight_scales.argtypes = [ctypes.POINTER(p),
                                          ctypes.POINTER(ctypes.c_int32)]
     lib.fm_get_weight_scales.restype = ctypes.c_int

@@ -4011,6 +4011,418 @@ void k_group_gemm_w4(GemmArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// MXFP8 activations for dtype 6 (fm_set_activation_quant(3), "mxfp8", W4A8;
+// DESIGN.md par.5q). The project's MX rule (k_quant_mx) on blocks of 32:
+//   amax = max|v|; e = 0 for a zero block, else the frexp exponent of
+//   amax / 448, clamped to -126..127; byte = 127 + e; q = e4m3_rne(v * 2^-e).
+// The exponent is taken from amax's bits (amax / 448 = 1.m / 1.75 *
+// 2^(E - 135), so frexp's exponent is E - 135, plus one where 1.m >= 1.75) and
+// the scaling is v_ldexp_f32: both exact, no division.
+//
+// Quantiser. Four lanes per block, each with ONE 16-byte load of 8 elements
+// and one 8-byte store, so a wave reads 1 KiB and writes 512 B contiguously;
+// amax is two xor-shuffles inside the quad, lane 0 of the quad writes the
+// scale byte. Grid-stride over the rows * K / 8 chunks. eC != nullptr is the
+// counted entry over [nRows / pEC, pEC, K] of k_quant_fp8_row: row e * pEC + m
+// is neither read nor written when m >= min(eC[e], EC).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) FM_NO_PK_F32
+void k_quant_mxfp8(const bf16* __restrict__ in, uint8_t* __restrict__ out8,
+                   uint8_t* __restrict__ scales, long long rows, int K,
+                   const uint32_t* __restrict__ eC, int EC, int pEC) {
+  const int cpr = K / 8;  // chunks per row; a multiple of 4
+  const long long total = rows * cpr;
+  for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < total;
+       c += (long long)gridDim.x * 256) {
+    // (a quad shares its row, total is a multiple of 4: quads stay whole)
+    const long long r = c / cpr;
+    const int ch = (int)(c - r * cpr);
+    bool live = true;
+    if (eC) live = (uint32_t)(r % pEC) < min(eC[r / pEC], (uint32_t)EC);
+    u32x4 w{0u, 0u, 0u, 0u};
+    if (live) w = *reinterpret_cast<const u32x4*>(in + r * K + ch * 8);
+    float v[8];
+    float m = 0.0f;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      v[2 * d] = __uint_as_float(w[d] << 16);
+      v[2 * d + 1] = __uint_as_float(w[d] & 0xFFFF0000u);
+      m = fmaxf(m, fmaxf(fabsf(v[2 * d]), fabsf(v[2 * d + 1])));
+    }
+    m = fmaxf(m, __shfl_xor(m, 1, 64));
+    m = fmaxf(m, __shfl_xor(m, 2, 64));
+    if (!live) continue;
+    int e = 0;
+    if (m > 0.0f) {
+      const uint32_t mb = __float_as_uint(m);
+      e = (int)(mb >> 23) - 135 + ((mb & 0x7FFFFFu) >= 0x600000u ? 1 : 0);
+      e = min(max(e, -126), 127);
+    }
+    uint32_t q[2];
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+      float s[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)  // saturate (a block whose e was clamped)
+        s[i] = fminf(fmaxf(ldexpf(v[4 * d + i], -e), -448.0f), 448.0f);
+      uint32_t pk = __builtin_amdgcn_cvt_pk_fp8_f32(s[0], s[1], 0u, false);
+      q[d] = __builtin_amdgcn_cvt_pk_fp8_f32(s[2], s[3], pk, true);
+    }
+    *reinterpret_cast<uint2*>(out8 + r * K + ch * 8) = make_uint2(q[0], q[1]);
+    if ((ch & 3) == 0) scales[r * (K / 32) + (ch >> 2)] = (uint8_t)(127 + e);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Grouped GEMM, MXFP8 activations x MXFP4 weights (par.5q), on
+// v_mfma_scale_f32_16x16x128_f8f6f4 with an e2m1 first operand (cbsz 4) and
+// an e4m3 second operand: the instruction takes the packed nibbles as they
+// lie in HBM and applies both operands' E8M0 scales per 32 of K, so
+//   acc[m, n] = sum_b 2^(sA[m,b]-127) 2^(sW[n,b]-127) sum_{k in b} q[m,k] w[n,k]
+// is ONE accumulator chain over the whole K: no conversion, no scale multiply,
+// no fold. Products and scales are exact; only the fp32 order is the MFMA's.
+//
+// Fragment layout (probed on gfx950): the fp4 lane (row,
+// g = lane >> 4) carries k = 32 g .. + 31 of the tile in four registers, low
+// nibble first, and byte 0 of its scale register scales exactly that block;
+// the fp8 lane (row, h) carries k = 16 h .. + 15 in registers 0-3 and
+// k = 64 + 16 h .. + 15 in registers 4-7, and its scale byte scales block h.
+//
+// Tile: BM = 128, BK = 128, 512 threads = 2M x 4N waves, 3 stages. BN = 128
+// (76.5 KiB of LDS, at most 128 VGPRs: two blocks per CU), or 256 for the
+// gated up phase (102 KiB, one block per CU).
+// A stage: [128 rows][128 B] e4m3, 1 KiB DMA groups of 8 rows x 8 chunks; the
+//   chunk at position p of row R holds source chunk p ^ (R & 7). Lane (R, h)
+//   reads chunks h and 4 + h: two 16-byte LDS reads per fragment.
+// B stage: k_group_gemm_w4's: [BN rows][64 B], the chunk at position p of row
+//   R holds source chunk p ^ ((R >> 2) & 3); lane (R, g) reads chunk g whole.
+// Scale strip: ONE 4-byte-per-lane DMA per wave and stage: lanes 0-15 fetch
+//   the four scale bytes of this K tile of A rows 16 wave .. + 15, lanes
+//   16 .. 15 + BN / 8 those of B rows (BN / 8) wave .. ; [8][16 + BN / 8]
+//   dwords. A lane reads its byte (h of the A row, g of the B row) with one
+//   ds_read_u8 per fragment; the zero-extended byte is the scale operand.
+// So every wave has GPS = GPW_A + GPW_B + 1 loads per stage in flight and
+// one counted vmcnt wait serves them, as in k_group_gemm_w4.
+//
+// Walk, PHASE semantics, swapped operands (weights first: lane & 15 is the
+// output row, a fragment pair's registers are eight consecutive columns), the
+// B row interleave, GATED fragments and the epilogue are w4_gemm_job_body's.
+// a.A is e4m3 [rows, K] (strideAExpert in elements = bytes), a.aScales uint8
+// [rows, K / 32]; B and a.bScale exactly as k_group_gemm_w4 takes them.
+// ---------------------------------------------------------------------------
+constexpr int W4A8_STAGES = 3;
+template <int BN> __host__ __device__ constexpr int w4a8_lds_bytes() {
+  return W4A8_STAGES * (128 * 128 + BN * 64 + 8 * (16 + BN / 8) * 4) +
+         128 * 8 + 128 * 4 + 16;
+}
+
+template <int PHASE, bool GATED, int BN>
+__device__ __forceinline__ void w4a8_gemm_job_body(const GemmArgs& a,
+                                                   char* smemBase, int e,
+                                                   int m0, int n0) {
+  static_assert(GATED ? (PHASE == 0 && BN == 256) : BN == 128,
+                "128 output columns per tile");
+  constexpr int BM = 128, BK = 128, SE = W4A8_STAGES;
+  constexpr int SRW = BN / 8;            // B scale rows per wave
+  constexpr int WS = (16 + SRW) * 4;     // bytes of a wave's scale strip
+  constexpr int A_ST = BM * BK, B_ST = BN * BK / 2, S_ST = 8 * WS;
+  char* Abase = smemBase;                       // SE x [BM][128 B]
+  char* Bbase = Abase + SE * A_ST;              // SE x [BN][64 B]
+  char* Sbase = Bbase + SE * B_ST;              // SE x [8][16 + SRW] dwords
+  TPS* sTps = reinterpret_cast<TPS*>(Sbase + SE * S_ST);
+  float* sScale = reinterpret_cast<float*>(sTps + BM);
+  uint32_t* sRouted = reinterpret_cast<uint32_t*>(sScale + BM);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int K = a.K, N = a.N;
+  const int nK = K / BK;
+  const int nOut = GATED ? (N >> 1) : N;  // weight rows per projection
+
+  const TPS* tpsE = a.tokenIds ? a.tokenIds + (size_t)e * a.pEC : nullptr;
+  __syncthreads();  // prior job's LDS readers done
+  if (tid == 0)
+    *sRouted = tpsE ? min(a.eC[e], (uint32_t)a.EC) : (uint32_t)a.nRows;
+  __syncthreads();
+  const uint32_t routed = *sRouted;
+  if ((uint32_t)m0 >= routed) return;
+  const int mCap = a.tokenIds ? a.pEC : a.nRows;
+  const int we = a.segExpert ? a.segExpert[e] : e;
+  // slot / scaled / nSlot: as in gemm_job_body
+  const bool slot = (PHASE == 1) && (a.topk > 1 || a.slotAlways);
+  const bool scaled =
+      (PHASE == 1) && a.topk > 1 && !(a.nShared && e >= a.nRoutedE);
+  const int nSlot = a.topk + a.nShared;
+  if (tid < BM) {
+    TPS t{0u, 1.0f};
+    if ((uint32_t)(m0 + tid) < routed)
+      t = tpsE ? tpsE[m0 + tid] : TPS{(uint32_t)(m0 + tid), 1.0f};
+    sTps[tid] = t;
+    if constexpr (PHASE == 1) {
+      float sc = 1.0f;
+      if (scaled && (uint32_t)(m0 + tid) < routed)
+        sc = toF(reinterpret_cast<const bf16*>(
+                 a.gate_out)[(size_t)tpsTok(t.tokenIdx) * a.PX +
+                             a.expertOffset + e]) / t.probSum;
+      sScale[tid] = sc;
+    }
+  }
+  __syncthreads();
+
+  const char* __restrict__ Ag = reinterpret_cast<const char*>(a.A);
+  const char* __restrict__ ASg = reinterpret_cast<const char*>(a.aScales);
+  const char* __restrict__ Bg =
+      reinterpret_cast<const char*>(a.B) + (size_t)we * a.strideBExpert;
+  const char* __restrict__ Sg =
+      reinterpret_cast<const char*>(a.bScale) + (size_t)we * a.bScaleStride;
+  const int nBase = GATED ? (n0 >> 1) : n0;
+  const int sPitch = K / 32;  // scale bytes per row, of A and of B
+
+  // tile-local B row -> weight row of its projection (clamped), and whether
+  // the row is a Wglu row (w4_gemm_job_body's map)
+  auto bRowOf = [&](int Rl, bool& glu) -> int {
+    const int wcR = Rl / (BN / 4);
+    const int ni = (Rl % (BN / 4)) >> 4;
+    const int i = Rl & 15;
+    const int j = GATED ? (ni >> 1) : ni;
+    glu = GATED && (ni & 1) == 0;
+    return min(nBase + wcR * 32 + 8 * (i >> 2) + 4 * j + (i & 3), nOut - 1);
+  };
+  // tile row -> row of a.A / a.aScales (rows past routed: a valid row whose
+  // products land in output rows that are not written)
+  const size_t aRow0 = (size_t)e * a.strideAExpert / (size_t)K;
+  auto aRowOf = [&](int row) -> size_t {
+    return aRow0 + ((PHASE == 0) ? (size_t)tpsTok(sTps[row].tokenIdx)
+                                 : (size_t)min(m0 + row, mCap - 1));
+  };
+
+  constexpr int GPW_A = BM / 8 / 8;   // 1 KiB groups of 8 A rows, per wave
+  constexpr int GPW_B = BN / 16 / 8;  // 1 KiB groups of 16 B rows, per wave
+  constexpr int GPS = GPW_A + GPW_B + 1;
+  const char* aSrc[GPW_A];
+  const char* bSrc[GPW_B];
+#pragma unroll
+  for (int i = 0; i < GPW_A; ++i) {
+    const int row = (wave * GPW_A + i) * 8 + (lane >> 3);
+    aSrc[i] = Ag + aRowOf(row) * (size_t)K + (((lane & 7) ^ (row & 7)) * 16);
+  }
+#pragma unroll
+  for (int i = 0; i < GPW_B; ++i) {
+    const int Rl = (wave * GPW_B + i) * 16 + (lane >> 2);
+    bool glu;
+    const int prow = bRowOf(Rl, glu);
+    bSrc[i] = Bg + (glu ? a.gluOffset : 0) + (size_t)prow * (K / 2) +
+              (((lane & 3) ^ ((Rl >> 2) & 3)) * 16);
+  }
+  // scale strip: lanes 0-15 an A row, lanes 16 .. 15 + SRW a B row
+  const char* sSrc;
+  if (lane < 16) {
+    sSrc = ASg + aRowOf(wave * 16 + lane) * (size_t)sPitch;
+  } else {
+    bool glu;
+    const int prow = bRowOf(wave * SRW + ((lane - 16) & (SRW - 1)), glu);
+    sSrc = Sg + (glu ? a.bScaleGlu : 0) + (size_t)prow * sPitch;
+  }
+  auto stage = [&](int kb, int buf) {
+#pragma unroll
+    for (int i = 0; i < GPW_A; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(aSrc[i] + kb * BK),
+          (las_u32*)(Abase + buf * A_ST + (wave * GPW_A + i) * 1024), 16, 0,
+          0);
+#pragma unroll
+    for (int i = 0; i < GPW_B; ++i)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(bSrc[i] + kb * (BK / 2)),
+          (las_u32*)(Bbase + buf * B_ST + (wave * GPW_B + i) * 1024), 16, 0,
+          0);
+    if (lane < 16 + SRW)
+      __builtin_amdgcn_global_load_lds(
+          (gas_u32*)(sSrc + kb * 4),
+          (las_u32*)(Sbase + buf * S_ST + wave * WS), 4, 0, 0);
+  };
+
+  const int wr = wave >> 2, wc = wave & 3;
+  constexpr int MI = BM / 32, NF = BN / 64;
+  f32x4 accv[MI][NF];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) accv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  const int rl = lane & 15;
+  const int gk = lane >> 4;
+  // this lane's LDS offsets: A chunks gk and 4 + gk of its rows (R & 7 is
+  // rl & 7 for every mi), its B chunk, and its two scale bytes
+  const int aOff0 = (wr * (BM / 2) + rl) * BK + ((gk ^ (rl & 7)) * 16);
+  const int aOff1 = (wr * (BM / 2) + rl) * BK + (((4 + gk) ^ (rl & 7)) * 16);
+  const int asOff = (wr * 4) * WS + rl * 4 + gk;  // + mi * WS
+  int bOff[NF], bsOff[NF];
+#pragma unroll
+  for (int ni = 0; ni < NF; ++ni) {
+    const int Rl = wc * (BN / 4) + ni * 16 + rl;
+    bOff[ni] = Rl * 64 + ((gk ^ ((Rl >> 2) & 3)) * 16);
+    bsOff[ni] = (Rl / SRW) * WS + (16 + (Rl % SRW)) * 4 + gk;
+  }
+
+  stage(0, 0);
+  if (nK > 1) {
+    stage(1, 1);
+    wait_vmcnt<GPS>();  // tile 0 landed; tile 1 in flight
+  } else {
+    wait_vmcnt<0>();
+  }
+  __builtin_amdgcn_s_barrier();
+  for (int t = 0; t < nK; ++t) {
+    const int pre = t + SE - 1;  // tile staged this iteration
+    const bool stageNow = pre < nK;
+    const char* Al = Abase + (t % SE) * A_ST;
+    const char* Bl = Bbase + (t % SE) * B_ST;
+    const uint8_t* Sl =
+        reinterpret_cast<const uint8_t*>(Sbase + (t % SE) * S_ST);
+    __builtin_amdgcn_s_setprio(1);
+    i32x8 af[MI];
+    int as[MI];
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+      const u32x4 lo =
+          *reinterpret_cast<const u32x4*>(&Al[aOff0 + mi * 16 * BK]);
+      const u32x4 hi =
+          *reinterpret_cast<const u32x4*>(&Al[aOff1 + mi * 16 * BK]);
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        af[mi][d] = (int)lo[d];
+        af[mi][4 + d] = (int)hi[d];
+      }
+      as[mi] = Sl[asOff + mi * WS];
+    }
+    i32x8 bw[NF];
+    int bs[NF];
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni) {
+      const u32x4 w = *reinterpret_cast<const u32x4*>(&Bl[bOff[ni]]);
+      // registers 4-7 of an fp4 operand are not read by the instruction
+      bw[ni] = i32x8{(int)w[0], (int)w[1], (int)w[2], (int)w[3], 0, 0, 0, 0};
+      bs[ni] = Sl[bsOff[ni]];
+    }
+    // fragments are read BEFORE the next stage is issued (see
+    // aq_gemm_job_body: the compiler's own vmcnt(0) ahead of LDS reads)
+    if (stageNow) stage(pre, pre % SE);
+#pragma unroll
+    for (int ni = 0; ni < NF; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+        accv[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+            bw[ni], af[mi], accv[mi][ni], 4 /*fp4*/, 0 /*fp8*/, 0, bs[ni], 0,
+            as[mi]);
+    __builtin_amdgcn_s_setprio(0);
+    if (stageNow) wait_vmcnt<GPS>(); else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+  }
+
+  // epilogue (w4_gemm_job_body's): lane & 15 is the row of fragment mi; the
+  // lane's registers of output fragments 0 and 1 are columns oBase .. + 7
+  const int act = a.act;
+  const int oBase = nBase + wc * 32 + 8 * gk;
+  float bv[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) bv[c] = 0.f;
+  if (a.bias) {
+    const bf16* bptr = reinterpret_cast<const bf16*>(a.bias) +
+                       (a.strideBExpert ? (size_t)we * nOut : 0);
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+      if (oBase + c < nOut) bv[c] = toF(bptr[oBase + c]);
+  }
+  bf16* outBase;
+  if constexpr (PHASE == 1)
+    outBase = reinterpret_cast<bf16*>(slot ? (void*)a.O32 : a.moe_out);
+  else
+    outBase = reinterpret_cast<bf16*>(a.out) + (size_t)e * a.strideOExpert;
+  const long long rowPitch = (PHASE == 1) ? a.H : nOut;
+  const bool wideOK = (rowPitch & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(outBase) & 15) == 0;
+  const bool vecOK = (rowPitch & 3) == 0 &&
+                     (reinterpret_cast<uintptr_t>(outBase) & 7) == 0;
+  const int nValid = nOut - oBase;
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi) {
+    const int row = wr * (BM / 2) + mi * 16 + rl;
+    const int m = m0 + row;
+    if ((uint32_t)m >= routed || nValid <= 0) continue;  // not written
+    bf16* orow;
+    float rowScale = 1.0f;
+    if constexpr (PHASE == 1) {
+      const TPS tp = sTps[row];
+      if (slot) {
+        orow = outBase + ((size_t)tpsTok(tp.tokenIdx) * nSlot +
+                          tpsJ(tp.tokenIdx)) * rowPitch;
+        rowScale = sScale[row];
+      } else {
+        orow = outBase + (size_t)tpsTok(tp.tokenIdx) * rowPitch;
+      }
+    } else {
+      orow = outBase + (size_t)m * rowPitch;
+    }
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float x;
+        if constexpr (GATED) {
+          x = gate_act(accv[mi][2 * j][r], act) * accv[mi][2 * j + 1][r];
+        } else {
+          x = accv[mi][j][r] + bv[4 * j + r];
+          if constexpr (PHASE == 0)
+            x = (act == 0)
+                ? fmaxf(x, 0.0f)
+                : 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+          if constexpr (PHASE == 1)
+            if (slot) x = x * rowScale;
+        }
+        v[4 * j + r] = x;
+      }
+    if (wideOK) {
+      const uint32_t w[4] = {
+          ETr<bf16>::pack2(v[0], v[1]), ETr<bf16>::pack2(v[2], v[3]),
+          ETr<bf16>::pack2(v[4], v[5]), ETr<bf16>::pack2(v[6], v[7])};
+      storeRow8(orow + oBase, w, nValid);
+    } else {
+      const float lo[4] = {v[0], v[1], v[2], v[3]};
+      const float hi[4] = {v[4], v[5], v[6], v[7]};
+      storeRow4<false>(orow + oBase, lo, nValid, vecOK);
+      if (nValid > 4) storeRow4<false>(orow + oBase + 4, hi, nValid - 4, vecOK);
+    }
+  }
+}
+
+template <int PHASE, bool GATED, int BN>
+__global__ __launch_bounds__(512, BN == 256 ? 2 : 4) FM_NO_PK_F32
+void k_group_gemm_w4a8(GemmArgs a) {
+  constexpr int BM = 128;
+  __shared__ __attribute__((aligned(16))) char smem[w4a8_lds_bytes<BN>()];
+  const int mT = a.totalJobs > 0 ? a.jobsMT : gridDim.x;
+  const int nT = a.totalJobs > 0 ? a.jobsNT : gridDim.y;
+  const int gstride = gridDim.x * gridDim.y * gridDim.z;
+  const int nBlocks = a.totalJobs > 0 ? a.totalJobs : gstride;
+  const int lin0 =
+      blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int qx = nBlocks / 8, rx = nBlocks % 8;
+  for (int jl = lin0; jl < nBlocks; jl += gstride) {
+    const int xcd = jl % 8, pos = jl / 8;
+    const int swz = a.noRemap
+        ? jl
+        : (xcd < rx ? xcd * (qx + 1) : rx * (qx + 1) + (xcd - rx) * qx) + pos;
+    const int e = swz / (mT * nT);
+    const int rem = swz % (mT * nT);
+    w4a8_gemm_job_body<PHASE, GATED, BN>(a, smem, e, (rem % mT) * BM,
+                                         (rem / mT) * BN);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // fp32 grouped GEMM (config-1 "CPU correctness plumbing" shapes; VALU
 // tiled). 64x64 tile, 256 threads, each thread a 4x4 sub-block, BK=16.
 // Same phase semantics as the bf16 kernel.
@@ -5347,6 +5759,9 @@ static int launch_quant_row(hipStream_t st, const void* in, uint8_t* out,
                             uint8_t* scales, long long nRows, int K,
                             const uint32_t* eC = nullptr, int EC = 0,
                             int pEC = 1);
+static int launch_quant_mxfp8(hipStream_t st, const void* in, uint8_t* out,
+                              uint8_t* scales, long long nRows, int K,
+                              const uint32_t* eC, int EC, int pEC);
 
 namespace {
 
@@ -5405,6 +5820,8 @@ struct State {
   // allocated by the set call; xs / xMs then hold fp32 [rows, K/128])
   int actQuant = 0;          // 0 off, 1 group128, 2 token (par.5o: xs / xMs
                              // hold fp32 [rows]); part of the graph key
+                             // 3 mxfp8 (dtype 6, par.5q: xs / xMs hold E8M0
+                             // bytes [rows, K/32])
   float* O32 = nullptr;      // [S, H] (staged-API combine accumulator)
   void* cbuf = nullptr;      // [S, k, H] Element: non-atomic combine slots
   uint8_t* kept = nullptr;   // [S, k] capacity-kept mask (gate-written)
@@ -6492,13 +6909,45 @@ int fm_set_weight_mx_scales(const uint8_t* scales) {
 
 int fm_set_activation_quant(int mode) {
   if (!g.initialized) { setErr("not initialized"); return FM_ERR_STATE; }
-  if (mode != 0 && mode != 1 && mode != 2) {
+  if (mode != 0 && mode != 1 && mode != 2 && mode != 3) {
     snprintf(g_err, sizeof(g_err),
-             "activation quant mode must be 0 (off), 1 (group128) or 2 "
-             "(token); got %d", mode);
+             "activation quant mode must be 0 (off), 1 (group128), 2 "
+             "(token) or 3 (mxfp8); got %d", mode);
     return FM_ERR_UNSUPPORTED;
   }
-  if (mode != 0) {
+  if (mode == 3) {
+    if (g.cfg.dtype != 6) {
+      snprintf(g_err, sizeof(g_err),
+               "activation quant mxfp8 needs MXFP4 expert weights: "
+               "torch_dtype must be 6, the config has torch_dtype %d",
+               (int)g.cfg.dtype);
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (g.cfg.is_training) {
+      setErr("activation quant mxfp8 is not supported with is_training 1 "
+             "(inference only)");
+      return FM_ERR_UNSUPPORTED;
+    }
+    if (!g.x8) {
+      // here, outside any capture: e4m3 rows and one E8M0 byte per 32 of K,
+      // for the forward (S rows) and the EP entry points (nLxAlloc * pEC)
+      const size_t qRows = std::max((size_t)g.S, (size_t)g.nLxAlloc * g.pEC);
+      const size_t mRows = (size_t)g.nLxAlloc * g.pEC;
+      uint8_t *a8 = nullptr, *as = nullptr, *m8 = nullptr, *ms = nullptr;
+      const bool ok = hipMalloc(&a8, qRows * g.H) == hipSuccess &&
+                      hipMalloc(&as, qRows * (g.H / 32)) == hipSuccess &&
+                      hipMalloc(&m8, mRows * g.P) == hipSuccess &&
+                      hipMalloc(&ms, mRows * (g.P / 32)) == hipSuccess;
+      if (!ok) {  // a refused call changes nothing
+        (void)hipFree(a8); (void)hipFree(as); (void)hipFree(m8);
+        (void)hipFree(ms);
+        (void)hipGetLastError();
+        setErr("activation quant: workspace allocation failed");
+        return FM_ERR_HIP;
+      }
+      g.x8 = a8; g.xs = as; g.xM8 = m8; g.xMs = ms;
+    }
+  } else if (mode != 0) {
     const char* name = mode == 1 ? "group128" : "token";
     if (g.cfg.dtype != 4) {
       snprintf(g_err, sizeof(g_err),
@@ -6601,6 +7050,27 @@ int fm_quant_fp8_row_counted(void* stream, const void* in, void* out8,
                           reinterpret_cast<uint8_t*>(scales),
                           n_slices * pitch_rows, (int)K, counts, (int)cap,
                           (int)std::max<int64_t>(pitch_rows, 1));
+}
+
+int fm_quant_mxfp8(void* stream, const void* in, void* out8, uint8_t* scales,
+                   int64_t rows, int64_t K) {
+  return fm_quant_mxfp8_counted(stream, in, out8, scales, nullptr, 1, rows,
+                                rows, K);
+}
+
+int fm_quant_mxfp8_counted(void* stream, const void* in, void* out8,
+                           uint8_t* scales, const uint32_t* counts,
+                           int64_t n_slices, int64_t pitch_rows, int64_t cap,
+                           int64_t K) {
+  if (n_slices < 0 || pitch_rows < 0 || K <= 0 || K % 32 != 0 ||
+      K > INT32_MAX) {
+    setErr("fm_quant_mxfp8: K must be a positive multiple of 32");
+    return FM_ERR_SHAPE;
+  }
+  return launch_quant_mxfp8(reinterpret_cast<hipStream_t>(stream), in,
+                            reinterpret_cast<uint8_t*>(out8), scales,
+                            n_slices * pitch_rows, (int)K, counts, (int)cap,
+                            (int)std::max<int64_t>(pitch_rows, 1));
 }
 
 int fm_get_weight_scales(const float** scales, int32_t* granularity) {
@@ -7158,12 +7628,32 @@ static int launch_quant_row(hipStream_t st, const void* in, uint8_t* out,
   return FM_OK;
 }
 
+// fm_set_activation_quant(3): bf16 rows -> e4m3 + E8M0 bytes [rows, K/32]
+// (par.5q); four lanes per block of 32. eC: the counted entry, as above.
+static int launch_quant_mxfp8(hipStream_t st, const void* in, uint8_t* out,
+                              uint8_t* scales, long long nRows, int K,
+                              const uint32_t* eC, int EC, int pEC) {
+  if (nRows <= 0) return FM_OK;
+  const int grid =
+      (int)std::min<long long>(DIVUP(nRows * (K / 8), 256), 2048);
+  hipLaunchKernelGGL(k_quant_mxfp8, dim3(grid), dim3(256), 0, st,
+                     reinterpret_cast<const bf16*>(in), out, scales, nRows, K,
+                     eC, EC, pEC);
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
 // the quantiser of the active mode over plain rows (x, packed EP rows)
 static int launch_quant_act(hipStream_t st, const void* in, uint8_t* out,
                             uint8_t* scales, long long nRows, int K) {
+  if (g.actQuant == 3)
+    return launch_quant_mxfp8(st, in, out, scales, nRows, K, nullptr, 0, 1);
   return g.actQuant == 2 ? launch_quant_row(st, in, out, scales, nRows, K)
                          : launch_quant_g128(st, in, out, scales, nRows, K);
 }
+
+static int launch_group_gemm_w4a8(hipStream_t st, int phase, const GemmArgs& a,
+                                  int M, int nE);
 
 // fm_set_activation_quant(1): the e4m3 x e4m3 grouped GEMM (par.5n). The
 // caller describes the plain problem like launch_group_gemm's callers, with
@@ -7175,6 +7665,8 @@ static int launch_quant_act(hipStream_t st, const void* in, uint8_t* out,
 // the 128x256 tile under the down phase's rule.
 static int launch_group_gemm_aq(hipStream_t st, int phase, const GemmArgs& a,
                                 int M, int nE) {
+  // mode 3 (dtype 6): the MXFP8 x MXFP4 kernels, one family for every phase
+  if (g.actQuant == 3) return launch_group_gemm_w4a8(st, phase, a, M, nE);
   const bool gated = phase == 0 && a.act >= 2;
   if (gated && a.bias) {
     setErr("b_up is not supported with a gated hidden_act (2/3)");
@@ -7279,6 +7771,49 @@ static int launch_group_gemm_w4(hipStream_t st, int phase, const GemmArgs& a,
                        st, aa);
   else
     hipLaunchKernelGGL((k_group_gemm_w4<2, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  FM_HIP_CHECK(hipGetLastError());
+  return FM_OK;
+}
+
+// fm_set_activation_quant(3) (par.5q): k_group_gemm_w4a8 on the walk of
+// launch_group_gemm_w4; a.A / a.aScales are the quantised rows. The ungated
+// kernels hold two blocks per CU, the gated up kernel one.
+static int launch_group_gemm_w4a8(hipStream_t st, int phase, const GemmArgs& a,
+                                  int M, int nE) {
+  const bool gated = phase == 0 && a.act >= 2;
+  if (gated && a.bias) {
+    setErr("b_up is not supported with a gated hidden_act (2/3)");
+    return FM_ERR_UNSUPPORTED;
+  }
+  GemmArgs aa = a;
+  aa.N = gated ? 2 * a.N : a.N;
+  aa.strideBExpert = a.strideBExpert / 2;
+  aa.gluOffset = gated ? (long long)a.N * a.K : 0;  // slot 0 -> slot 2, bytes
+  aa.splitK = 1;
+  aa.noRemap = 0;
+  aa.totalJobs = 0;
+  const int nCU = g.nCU > 0 ? g.nCU : 256;
+  dim3 grid(DIVUP(M, 128), DIVUP(aa.N, gated ? 256 : 128), nE);
+  const int J = grid.x * grid.y * nE;
+  const int resident = (gated ? 1 : 2) * nCU;  // blocks per CU by LDS
+  if (J > resident) {
+    aa.totalJobs = J;
+    aa.jobsMT = grid.x;
+    aa.jobsNT = grid.y;
+    grid = dim3(resident, 1, 1);
+  }
+  if (gated)
+    hipLaunchKernelGGL((k_group_gemm_w4a8<0, true, 256>), grid, dim3(512), 0,
+                       st, aa);
+  else if (phase == 0)
+    hipLaunchKernelGGL((k_group_gemm_w4a8<0, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  else if (phase == 1)
+    hipLaunchKernelGGL((k_group_gemm_w4a8<1, false, 128>), grid, dim3(512), 0,
+                       st, aa);
+  else
+    hipLaunchKernelGGL((k_group_gemm_w4a8<2, false, 128>), grid, dim3(512), 0,
                        st, aa);
   FM_HIP_CHECK(hipGetLastError());
   return FM_OK;
@@ -7391,7 +7926,10 @@ static int moe_forward_impl(hipStream_t st, const void* x, const void* gate_w,
     // the intermediate, after activation / gating and its bf16 rounding: a
     // separate pass over xM (the fused epilogue is an open item, par.5n)
     // (token: only the rows the up GEMM wrote, m < min(eC[e], EC))
-    rc = g.actQuant == 2
+    rc = g.actQuant == 3
+        ? launch_quant_mxfp8(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC,
+                             g.P, g.eC, g.EC, g.pEC)
+        : g.actQuant == 2
         ? launch_quant_row(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC, g.P,
                            g.eC, g.EC, g.pEC)
         : launch_quant_g128(st, g.xM, g.xM8, g.xMs, (long long)nZ * g.pEC,

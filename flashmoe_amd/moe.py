@@ -343,7 +343,7 @@ def pack_weight_mx_scales(up, down, glu=None):
                      dim=1).contiguous()
 
 
-ACTIVATION_QUANT_MODES = {None: 0, "group128": 1, "token": 2}
+ACTIVATION_QUANT_MODES = {None: 0, "group128": 1, "token": 2, "mxfp8": 3}
 
 
 def set_activation_quant(mode):
@@ -354,17 +354,25 @@ def set_activation_quant(mode):
     with whichever weight scales are attached. "token" (par.5o): one scale
     for the whole row (compressed-tensors FP8-dynamic: activations strategy
     token, dynamic true), with per-channel weight scales or none; it and
-    weight block scales exclude each other. None: bf16 activations (the
-    default; initialize and finalize reset to it). Needs H and P multiples of
-    128 and an inference config."""
+    weight block scales exclude each other. "mxfp8" (torch_dtype 6 only,
+    par.5q): MXFP8 activations over the MXFP4 expert weights (W4A8): blocks
+    of 32 along K, e4m3 elements with one E8M0 scale byte each, both expert
+    GEMMs on the scaled MFMA. None: bf16 activations (the default; initialize
+    and finalize reset to it). Needs H and P multiples of 128 and an
+    inference config."""
     if not _state["initialized"]:
         raise RuntimeError("Must call initialize() first")
     if mode not in ACTIVATION_QUANT_MODES:
-        raise ValueError(f"activation_quant must be None, 'group128' or "
-                         f"'token'; got {mode!r}")
+        raise ValueError(f"activation_quant must be None, 'group128', "
+                         f"'token' or 'mxfp8'; got {mode!r}")
     cfg = _state["cfg"]
     if mode is not None:
-        if cfg["torch_dtype"] != 4:
+        if mode == "mxfp8" and cfg["torch_dtype"] != 6:
+            raise ValueError(
+                f"activation quant mxfp8 needs MXFP4 expert weights "
+                f"(torch_dtype 6); the initialized config has torch_dtype "
+                f"{cfg['torch_dtype']}")
+        if mode != "mxfp8" and cfg["torch_dtype"] != 4:
             raise ValueError(
                 f"activation quant needs fp8 expert weights with bf16 "
                 f"activations (torch_dtype 4); the initialized config has "
@@ -387,7 +395,7 @@ def set_activation_quant(mode):
 
 
 def get_activation_quant():
-    """The active mode: None, "group128" or "token"
+    """The active mode: None, "group128", "token" or "mxfp8"
     (fm_get_activation_quant)."""
     if not _state["initialized"]:
         raise RuntimeError("Must call initialize() first")
@@ -641,8 +649,8 @@ def moe_forward(input, gate_weights, expert_weights, weight_scales=None,
     tensor as for set_weight_scales; one that is not the attached tensor is
     attached first, None leaves the attachment as it is. weight_block_scales
     (torch_dtype 4): the same for set_weight_block_scales; pass one kind.
-    activation_quant: "group128", "token" or None sets that mode first
-    (set_activation_quant) when it is not the active one; left out, the mode
+    activation_quant: "group128", "token", "mxfp8" or None sets that mode
+    first (set_activation_quant) when it is not the active one; left out, the mode
     stays as it is. weight_mx_scales (torch_dtype 6): the same for
     set_weight_mx_scales."""
     import torch

@@ -261,15 +261,16 @@ int fm_set_weight_block_scales(const float* scales);
  * Read by fm_moe_forward, fm_moe_forward_phased, fm_expert_ffn,
  * fm_expert_ffn_segments and fm_expert_ffn_grouped, at S >= 128 and at
  * S in 1..127 (the masked 128-row tile). A dtype-6 forward always runs
- * k_group_gemm_w4: never k_moe_fused or k_decode_ffn, whatever FM_FUSED or
+ * k_group_gemm_w4 (k_group_gemm_w4a8 under fm_set_activation_quant(3)):
+ * never k_moe_fused or k_decode_ffn, whatever FM_FUSED or
  * FM_DECODE_FFN say, and FM_FORCE_MODE does not apply. Those entry points
  * return FM_ERR_STATE (the message names fm_set_weight_mx_scales) on dtype 6
  * while no scales are attached.
  * dtype 6 itself is refused by fm_initialize (FM_ERR_UNSUPPORTED) when
  * hidden_size or intermediate_size is not a multiple of 128 or with
  * is_training 1; fm_set_weight_scales(granularity 1),
- * fm_set_weight_block_scales and a non-zero fm_set_activation_quant are
- * refused on dtype 6.
+ * fm_set_weight_block_scales and fm_set_activation_quant(1 / 2) are
+ * refused on dtype 6 (mode 3, mxfp8, is the one made for it).
  * FM_ERR_UNSUPPORTED (the message names the cause): a non-null tensor with a
  * torch_dtype other than 6 (nothing changes). */
 int fm_set_weight_mx_scales(const uint8_t* scales);
@@ -305,15 +306,34 @@ int fm_set_weight_mx_scales(const uint8_t* scales);
  * combine scale and shared slices follow as in mode 1. No atomics: two
  * forwards are bit-identical. Everything else said of mode 1 holds, except
  * that mode 2 and weight block scales exclude each other.
+ * mode 3, "mxfp8" (dtype 6 only): MXFP8 activations over the
+ * MXFP4 expert weights, W4A8, the pairing the MX formats were specified for.
+ * The same two tensors are cut into blocks of 32 along K, each with one E8M0
+ * scale byte:
+ *   amax = max|v|;  e = 0 for a zero block, else the frexp exponent of
+ *                   amax / 448, clamped to -126..127
+ *   byte = 127 + e;  q = e4m3_rne(v * 2^-e)      (exact scaling, saturating)
+ * and both expert GEMMs run e4m3 x e2m1 on the scaled MFMA, which applies
+ * both operands' block scales itself:
+ *   acc[m, n] = sum_b 2^(sA[m,b]-127) * 2^(sW[n,b]-127)
+ *                     * sum_{k in b} q[m, k] * e2m1(w[n, k])
+ * with sW the attached fm_set_weight_mx_scales bytes. Products and scales are
+ * exact; one fp32 accumulator runs over the whole K. Bias, activation /
+ * gating, the bf16 rounding of the intermediate, the combine scale and shared
+ * slices are those of dtype 6 with mode 0; the gate reads bf16 x; no atomics.
+ * Read by the same five entry points, at S >= 128 and at S in 1..127; such a
+ * forward runs k_quant_mxfp8 and k_group_gemm_w4a8, never k_moe_fused or
+ * k_decode_ffn. With mode 0 a dtype-6 forward runs k_group_gemm_w4 as before.
  * Valid after fm_initialize; fm_initialize and fm_finalize reset to 0. A set
  * call is part of the captured forward graph's key, and the first set to a
- * non-zero mode allocates the fp8 and scale workspaces, which serve both modes
- * (call it outside a stream capture).
+ * non-zero mode allocates the fp8 and scale workspaces, which serve every mode
+ * of the config's dtype (call it outside a stream capture).
  * FM_ERR_UNSUPPORTED (the message names the cause; the mode is unchanged): an
  * unknown mode; mode 1 or 2 with a torch_dtype other than 4, with hidden_size
  * or intermediate_size not a multiple of 128, or with is_training 1; mode 2
  * while weight block scales are attached, or with hidden_size or
- * intermediate_size above 16384.
+ * intermediate_size above 16384; mode 3 with a torch_dtype other than 6 or
+ * with is_training 1.
  * fm_get_activation_quant returns the mode, or -1 before fm_initialize. */
 int fm_set_activation_quant(int mode);
 int fm_get_activation_quant(void);
@@ -336,6 +356,18 @@ int fm_quant_fp8_row_counted(void* stream, const void* in, void* out8,
                              float* scales, const uint32_t* counts,
                              int64_t n_slices, int64_t pitch_rows, int64_t cap,
                              int64_t K);
+
+/* The mxfp8 quantiser on its own: `in` bf16 [rows, K] (K a multiple of 32,
+ * 16-byte aligned) -> out8 e4m3 bytes [rows, K] and scales E8M0 bytes
+ * [rows, K / 32], row-major. Needs no fm_initialize. The counted form is
+ * fm_quant_fp8_row_counted's: row m of slice e is neither read nor written
+ * when m >= min(counts[e], cap). */
+int fm_quant_mxfp8(void* stream, const void* in, void* out8, uint8_t* scales,
+                   int64_t rows, int64_t K);
+int fm_quant_mxfp8_counted(void* stream, const void* in, void* out8,
+                           uint8_t* scales, const uint32_t* counts,
+                           int64_t n_slices, int64_t pitch_rows, int64_t cap,
+                           int64_t K);
 
 /* Replaces _C.get_compiled_config (python_bindings.cu:170-183 /
  * flashmoe/ops.py:63-71): S, H, E, P, PX, element byte size. */

@@ -3,7 +3,7 @@
 Usage: python tools/shape_bench.py [--hidden-act A] [--shared N | --compose N]
                                    [--router qwen|v2|v3|sigmoid]
                                    [--weight-scales | --weight-block-scales]
-                                   [--activation-quant [group128|token]]
+                                   [--activation-quant [group128|token|mxfp8]]
                                    [S H P E topk [steps [dtype]]]
 Defaults to the BASELINE config-3 shape. Prints one JSON line with
 per-phase HIP-event timing (fm_moe_forward_phased). --hidden-act 2/3
@@ -39,7 +39,8 @@ the e4m3 x e4m3 expert GEMMs; it composes with both weight-scale flags,
 --hidden-act and --shared. dtype 6 (MXFP4 expert weights, DESIGN.md par.5p;
 H and P multiples of 128) draws uniform nibbles and E8M0 scale bytes in
 121..130 and attaches them with set_weight_mx_scales; its weight_bytes count
-the packed nibbles and the scales.
+the packed nibbles and the scales. --activation-quant mxfp8 (dtype 6 only,
+par.5q) sets set_activation_quant("mxfp8"): MXFP8 activations, W4A8.
 """
 import ctypes
 import json
@@ -96,7 +97,7 @@ if "--activation-quant" in argv:
     i = argv.index("--activation-quant")
     argv.pop(i)
     activation_quant = "group128"  # the bare flag
-    if i < len(argv) and argv[i] in ("group128", "token"):
+    if i < len(argv) and argv[i] in ("group128", "token", "mxfp8"):
         activation_quant = argv.pop(i)
 ab_runs = 0
 if "--decode-ab" in argv:
@@ -121,8 +122,8 @@ if weight_scales and dtype_code not in (4, 5):
 if weight_block_scales and (dtype_code != 4 or weight_scales):
     sys.exit("--weight-block-scales needs dtype 4 and excludes --weight-scales")
 
-if activation_quant and dtype_code != 4:
-    sys.exit("--activation-quant needs dtype 4")
+if activation_quant and dtype_code != (6 if activation_quant == "mxfp8" else 4):
+    sys.exit("--activation-quant needs dtype 4 (mxfp8: dtype 6)")
 
 adt, wdt = torch_dtype_of(dtype_code), weight_dtype_of(dtype_code)
 torch.manual_seed(47)
@@ -187,10 +188,10 @@ def measure(S):
         moe.set_weight_block_scales(w_scales)
     elif w_scales is not None:
         moe.set_weight_scales(w_scales)
-    if activation_quant:
-        moe.set_activation_quant(activation_quant)
     if mx_scales is not None:
         moe.set_weight_mx_scales(mx_scales)
+    if activation_quant:
+        moe.set_activation_quant(activation_quant)
     x = x_first if S == s_list[0] else \
         torch.randn(1, S, H, dtype=adt, device="cuda")
     x = x.view(cfg["mini_batch"], cfg["sequence_len"], H)
@@ -278,7 +279,8 @@ def measure(S):
                      + (" weight-scales" if weight_scales else "")
                      + (" weight-block-scales" if weight_block_scales else "")
                      + (" activation-quant" if activation_quant else "")
-                     + ("=token" if activation_quant == "token" else "")),
+                     + (f"={activation_quant}"
+                        if activation_quant in ("token", "mxfp8") else "")),
         "us_per_fwd": round(dt * 1e6, 1),
         "tokens_per_s": round(S / dt),
         "gemm_tflops_upper": round(flops / gemm_ms / 1e9, 1) if gemm_ms else None,
